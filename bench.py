@@ -14,22 +14,30 @@ the first child that exits non-zero takes its siblings down (SIGTERM, then SIGKI
 status, so a dead rank never leaves the others parked in a barrier.  It refuses to run with fewer visible
 devices than --gpus.
 
-Order of one run: rank 0 times the CPU baseline first (the oracle's restatement of the reference algorithm on
-the host cores, ~12 s, nothing on the GPU yet; the other ranks wait in the rendezvous, timeout 300 s), then the
-GPU phase -- warm-up, the K timed steps, the stream-ceiling calibration and a 100-exec spread leg on rank 0 (HIP
-events only, not part of `value`), the batch-1 configurations of BASELINE.json (`"configs"`: N = 1024 = C1's shape, C2 = 2^20,
-C5 = 2^24, `--config-execs` execs each with HIP events, one exec of each checked against the fp64 DFT; rank 0, not part of
-`value`), and for N > 1 the slab-movement leg (below).  The line carries "gpu_phase_s".
+Order of a plain run: set-up, warm-up, the K timed steps, `--dump-outputs DIR` if given (below), the line.  With `--full`
+rank 0 times the CPU baseline first (the oracle's restatement of the reference algorithm on the host cores, ~12 s,
+nothing on the GPU yet; the other ranks wait in the rendezvous, timeout 300 s), and after the timed steps come the
+stream-ceiling calibration and a 100-exec spread leg on rank 0 (HIP events only, not part of `value`), the batch-1
+configurations of BASELINE.json (`"configs"`: N = 1024 = C1's shape, C2 = 2^20, C5 = 2^24, `--config-execs` execs each with
+HIP events, one exec of each checked against the fp64 DFT; rank 0, not part of `value`), and for N > 1 the slab-movement
+leg (below).  Without `--full` those fields of the line are null.  The line carries "gpu_phase_s".
+
+Outputs (`--dump-outputs DIR`): after the timed steps, before any `--full` leg runs, every rank writes the spectrum its
+last timed step returned (the buffer `Forward.proc` hands back: the source for even log2 N, the plan's second buffer for
+odd log2 N), as float32 [re, im] pairs: `DIR/spectrum.npy` (N = 1) or
+`DIR/spectrum_rank<r>.npy`, shape (transforms, bins, 2).  A fixed sample of DUMP_SAMPLES complex values over all ranks:
+transforms of the rank's slab picked by a generator seeded with 0x5EED, the first bins of each (the whole transform when it
+fits).  The input is the seeded device generator's, so the same arguments give the same inputs from run to run.
 
 Timing: K steps inside barrier + torch.cuda.synchronize() brackets, wall clock, MAX over ranks.
-Because a forward FFT multiplies the RMS by 2^10 and `proc` works in place, the K steps run in
+Because a forward FFT multiplies the RMS by 2^10 and `proc` works in place (even log2 N), the K steps run in
 chunks of <= 8 with the input regenerated (at scale 2^-40) between chunks, outside the brackets,
 so fp32 never overflows to inf/NaN (benchmarks on degenerate data are not representative).
 HIP events on the launch stream time each step for the roofline object; for N > 1 the line carries every rank's
 own time ("per_rank_ms": its wall clock between the opening barrier and its own synchronize, before the closing
 barrier) and `roofline` is that of the SLOWEST rank.
 
-Movement (N > 1, SURVEY.md 8(e): "reported as a separate line", never part of `value`): after the timed steps
+Movement (`--full`, N > 1, SURVEY.md 8(e): "reported as a separate line", never part of `value`): after the timed steps
 rank 0 scatters one slab of MOVE_TRANSFORMS transforms to every rank and gathers them back through the library's
 own communicator (`fwa_comm_scatter` / `fwa_comm_gather`: grouped RCCL send / receive over xGMI), timed with HIP
 events; a watchdog prints the line without it if the exchange does not finish in MOVE_TIMEOUT_S.
@@ -59,6 +67,7 @@ RENDEZVOUS_TIMEOUT_S = 300      # init_process_group / collectives: a missing ra
                                 # or supervise() below), not by this timeout
 MOVE_TRANSFORMS = 256           # slab moved per rank by the movement leg (2 GiB at N = 2^20)
 MOVE_TIMEOUT_S = 120
+DUMP_SAMPLES = 1 << 22          # complex values --dump-outputs writes over all ranks (32 MiB as float32 pairs)
 
 
 def usable_cores():
@@ -226,22 +235,46 @@ def config_shapes(fw, dev, queue, enc, checker, reps):
     return out
 
 
+def dump_outputs(out_dir, fw, result, enc, n, batch, rank, world):
+    """--dump-outputs: the spectrum in `result`, the buffer the last timed `Forward.proc` returned, sampled as the module
+    docstring says, saved as float32 [re, im] pairs of shape (transforms, bins, 2)."""
+    import numpy as np
+    budget = max(1, DUMP_SAMPLES // world)
+    bins = min(n, budget)
+    count = min(batch, budget // bins)
+    picks = np.sort(np.random.default_rng(0x5EED).choice(batch, size=count, replace=False))
+    out = np.empty((count, bins, 2), dtype=np.float32)
+    for i, t in enumerate(picks):
+        y = result.map_read(offset=int(t) * n * fw.COMPLEX_BYTES, size=bins * fw.COMPLEX_BYTES, stream=enc)
+        out[i, :, 0] = y.real
+        out[i, :, 1] = y.imag
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, ("spectrum" if world == 1 else f"spectrum_rank{rank}") + ".npy"), out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: CPU baseline, copy ceilings, single-pass reference, spread, "
+                         "batch-1 configurations, slab movement (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write a seeded sample of the last step's spectrum to DIR/*.npy (float32)")
     ap.add_argument("--fft-len", type=int, default=1 << 20)
     ap.add_argument("--batch", type=int, default=4096, help="transforms per GPU")
     ap.add_argument("--group", type=int, default=0, help="override plan tunable (0 = default)")
     ap.add_argument("--streams", type=int, default=0, help="override plan tunable (0 = default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--spread", type=int, default=100, help="extra execs timed one by one after the K steps (0 = off)")
-    ap.add_argument("--no-movement", action="store_true", help="N > 1: skip the slab scatter / gather leg")
+    ap.add_argument("--spread", type=int, default=100, help="--full: extra execs timed one by one after the K steps (0 = off)")
+    ap.add_argument("--no-movement", action="store_true", help="--full, N > 1: skip the slab scatter / gather leg")
     ap.add_argument("--config-execs", type=int, default=200,
-                    help="execs per batch-1 configuration (C1's shape, C2, C5) timed after the headline on rank 0 (0 = off)")
+                    help="--full: execs per batch-1 configuration (C1's shape, C2, C5) timed after the headline on rank 0 (0 = off)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args)  # never returns
@@ -266,11 +299,11 @@ def main():
     if torch.cuda.device_count() <= device_index:
         raise SystemExit(f"bench.py: rank {rank} has no device {device_index} ({torch.cuda.device_count()} visible)")
 
-    # CPU baseline on rank 0 BEFORE the rendezvous and before anything runs on the GPU: afterwards the run is one
+    # --full: CPU baseline on rank 0 BEFORE the rendezvous and before anything runs on the GPU: afterwards the run is one
     # contiguous GPU phase.  The other ranks wait for rank 0's store inside init_process_group (RENDEZVOUS_TIMEOUT_S).
     cpu = None
     checker = None     # the oracle, when this run loaded it: also checks one exec of each batch-1 configuration (config_shapes)
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         import oracle  # checker only: times the CPU restatement of the reference algorithm beside the GPU number
         checker = oracle
         cores = usable_cores()
@@ -361,7 +394,7 @@ def main():
         t0 = time.perf_counter()
         for i in range(k):
             ev[done + i][0].record(enc)
-            plan.proc(enc)
+            result = plan.proc(enc)       # the buffer a caller receives (--dump-outputs)
             ev[done + i][1].record(enc)
         local_sync()
         t1 = time.perf_counter()
@@ -381,14 +414,17 @@ def main():
     per_rank_ev_ms = all_gather_f64(ev_ms)
     per_rank_first = all_gather_f64(float(first))
 
-    # calibration on the same stream, same run (rank 0): what a single streaming pass sustains on this box --
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, fw, result, enc, n, batch, rank, world)
+
+    # --full: calibration on the same stream, same run (rank 0): what a single streaming pass sustains on this box --
     #  * in place (every line read, then written back: the traffic of the one-launch FFT kernels; fwa_calib_copy with
     #    dst == src runs the normalize kernel: one workgroup per 64-KiB chunk, every wave walks 16 KiB, 32 nt loads in flight),
     #  * out of place (8 GiB -> another 8 GiB, the same launch shape).
     # With N > 1 in rehearsal the ranks share one GPU: calibration figures would mean nothing and are skipped.
     copy_gbps = stream_gbps = None
     spread = single_pass = shapes = None
-    if rank == 0 and not rehearse:
+    if rank == 0 and not rehearse and args.full:
         def rate(dst, src, nb, reps=3):
             dev.calib_copy(dst, src, nb, encoder=enc)
             a, b = fw.Event(dev), fw.Event(dev)
@@ -489,7 +525,7 @@ def main():
             "config": {"workload": f"1-D c2c fp32 FFT N={n} batch={batch} per GPU (BASELINE.json configs[2]"
                                    f"{'; configs[3] shape' if world > 1 else ''})",
                        "fft_len": n, "batch_per_gpu": batch, "parallelism": f"batch-sharded x{world}, no collective",
-                       "rehearsal": bool(rehearse),
+                       "rehearsal": bool(rehearse), "full": bool(args.full),
                        "dist_backend": (dist.get_backend() if use_dist else None),
                        "dist_world_size": (dist.get_world_size() if use_dist else None),
                        "slab_first_transform_per_rank": [int(v) for v in per_rank_first],
@@ -531,9 +567,9 @@ def main():
     # prints -- it makes no library or HIP call while the main thread is parked in a sync on a possibly wedged device.
     line = build_line() if rank == 0 else None
 
-    # ---- movement leg (N > 1; never part of `value`) -------------------------------------------------------------------
+    # ---- movement leg (--full, N > 1; never part of `value`) -----------------------------------------------------------
     movement = None
-    if use_dist and not args.no_movement:
+    if use_dist and args.full and not args.no_movement:
         if rehearse:
             movement = {"skipped": "rehearsal: RCCL refuses two ranks on one device (fwa_comm_* needs one GPU per rank)"}
         else:

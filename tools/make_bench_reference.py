@@ -63,7 +63,7 @@ def main():
     ref["traffic_source"] = (
         f"profiles/round{rnd}/a_pmc_fetch_summary.txt + a_pmc_write_summary.txt: (2*FETCH_SIZE + WRITE_SIZE)*1024 per dispatch "
         f"(means over {n1} dispatches each: k_p1_1m {f1:.1f} / {w1:.0f} KB, k_p2_1m {f2:.1f} / {w2:.0f} KB) x the 256 k_p1_1m + 256 "
-        f"k_p2_1m dispatches of one exec; separate rocprofv3 --pmc passes of `python3 bench.py --steps 2 --warmup 1 "
+        f"k_p2_1m dispatches of one exec; separate rocprofv3 --pmc passes of `python3 bench.py --full --steps 2 --warmup 1 "
         f"--no-cpu-baseline --spread 0` (tools/run_round_profiles.sh, taken BEFORE the bench line of the same job); the gfx950 "
         f"FETCH x2 rule checked in the same run on " + ", ".join(f"{k} ({v:.6g} KB)" for k, v in checks.items()) +
         " (k_copy reads 8 GiB, k_scale 16 GiB, k_small32<10> 32 GiB: FETCH_SIZE = 1/2 of the bytes); WRITE_SIZE exact on all of "

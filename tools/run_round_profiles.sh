@@ -10,7 +10,7 @@ O=gpurun_out/round$R
 mkdir -p $O
 # the profiled runs leave out the legs that launch the calibration kernels at other sizes (spread, batch-1 configurations): the
 # per-dispatch means of k_copy / k_scale / k_small32<10> then are the 8 / 16 / 32-GiB passes the FETCH x 2 rule is checked on
-B="python3 bench.py --no-cpu-baseline --spread 0 --config-execs 0"
+B="python3 bench.py --full --no-cpu-baseline --spread 0 --config-execs 0"
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- $B --steps 2 --warmup 1 > $O/pmc_fetch.log 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- $B --steps 2 --warmup 1 > $O/pmc_write.log 2>&1
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- $B --steps 5 --warmup 2 > $O/prof_default.log 2>&1
@@ -24,7 +24,7 @@ cp "$(find $O/prof_streams1 -name '*kernel_stats.csv' | head -1)" $O/a_kernel_st
 rm -rf $O/prof_default $O/prof_streams1 $O/pmc_fetch $O/pmc_write
 python3 tools/make_bench_reference.py $O $R "${FWA_COMMIT:-}" > $O/bench_reference.log 2>&1   # FWA_COMMIT=$(git rev-parse --short=12 HEAD) in the gpurun command line: the box has no .git
 cp profiles/bench_reference.json $O/bench_reference.json
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $O/a_bench_default.json 2> $O/bench_default.err
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > $O/a_bench_default.json 2> $O/bench_default.err
 echo "profiles done"
 if [ "${2:-}" = profiles-only ]; then exit 0; fi
 timeout -k 10 400 python3 tools/size_bench.py --lg-max 24 > $O/b_size_sweep_2GiB.jsonl 2>&1
