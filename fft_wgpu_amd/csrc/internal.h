@@ -69,8 +69,7 @@ struct fwa_ctx {
     int device = -1;
     hipDeviceProp_t prop{};
     mutable std::string err;
-    bool setup_1m_done = false;
-    bool setup_small_done = false;
+    uint32_t kernel_families = 0;  // kernel families whose dynamic-LDS limits are raised (plan.cpp: setup_path)
     // plan cache: (fft_len, path, factor signature) -> tables; ring allocations of destroyed plans by size
     std::map<std::tuple<uint32_t, int64_t, uint32_t>, std::shared_ptr<fwa_int::Tables>> tables;
     std::vector<std::pair<uint64_t, void *>> free_rings;  // rings of destroyed plans, oldest first

@@ -134,7 +134,7 @@ static hipError_t launch_chunk_dir(const v2f *src, v2f *dst, const v2f *tw, uint
                                    hipStream_t st)
 {
     const uint64_t blocks = (n_samples + 8191) / 8192;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    if (hipError_t e = check_grid(blocks); e != hipSuccess) return e;
     const dim3 g((uint32_t)blocks), b(256);
     switch (lg_n) {
         case 1: hipLaunchKernelGGL((k_chunk<1, DIR>), g, b, 0, st, src, dst, tw, n_samples, scale); break;

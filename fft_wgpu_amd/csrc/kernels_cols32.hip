@@ -180,86 +180,79 @@ __global__ __launch_bounds__(512, 4) void k_colsw(const v2f *__restrict__ in, v2
     FWA_STAMP(3);
 }
 
-template <int LGN>
-static int colsw_lds() { return Rows32<LGN, (1 << (14 - LGN))>::LDS_BYTES + ((1 << (LGN - 5)) + (1024 >> LGN)) * (1 << (14 - LGN)) * 8; }
-template <int LGN>
-static const void *colsw_kernel(int dir, bool ring)
-{
-    constexpr int CW = 1 << (14 - LGN);
-    return dir == FWD ? (ring ? reinterpret_cast<const void *>(&k_colsw<LGN, CW, FWD, AUX_SC1>) : reinterpret_cast<const void *>(&k_colsw<LGN, CW, FWD, AUX_NT>))
-                      : (ring ? reinterpret_cast<const void *>(&k_colsw<LGN, CW, INV, AUX_SC1>) : reinterpret_cast<const void *>(&k_colsw<LGN, CW, INV, AUX_NT>));
-}
-
 bool colsw_supported(uint32_t lg_l) { return lg_l == 8 || lg_l == 9; }
 uint32_t colsw_width(uint32_t lg_l) { return 1u << (14 - lg_l); }
+bool cols32_supported(uint32_t lg_l) { return lg_l == 11; }
 
-hipError_t prepare_colsw(uint32_t lg_l)
+// Pickers: the output of both column kernels goes through to the ring slab the next pass reads (sc1).
+static KernelLaunch colsw_launch(int dir, uint32_t lg_l)
 {
-    if (!colsw_supported(lg_l)) return hipErrorInvalidValue;
+    auto of = [dir](auto lgn_) -> KernelLaunch {
+        constexpr int LGN = decltype(lgn_)::value, CW = 1 << (14 - LGN);
+        return {dir == FWD ? reinterpret_cast<const void *>(&k_colsw<LGN, CW, FWD, AUX_SC1>)
+                           : reinterpret_cast<const void *>(&k_colsw<LGN, CW, INV, AUX_SC1>),
+                512, Rows32<LGN, CW>::LDS_BYTES + ((1 << (LGN - 5)) + (1024 >> LGN)) * CW * 8};
+    };
+    if (lg_l == 9) return of(std::integral_constant<int, 9>{});
+    if (lg_l == 8) return of(std::integral_constant<int, 8>{});
+    return {};
+}
+static KernelLaunch cols32_launch(int dir, uint32_t lg_l)
+{
+    if (!cols32_supported(lg_l)) return {};
+    return {dir == FWD ? reinterpret_cast<const void *>(&k_cols32<11, 16, FWD, AUX_SC1>)
+                       : reinterpret_cast<const void *>(&k_cols32<11, 16, INV, AUX_SC1>),
+            1024, Rows32<11, 16>::LDS_BYTES + 32 * 16 * 8};
+}
+
+hipError_t setup_colsw_kernels()
+{
     hipError_t e = hipSuccess;
-    for (int dir : {FWD, INV})
-        for (bool ring : {true, false})
-            if (e == hipSuccess)
-                e = lg_l == 9 ? hipFuncSetAttribute(colsw_kernel<9>(dir, ring), hipFuncAttributeMaxDynamicSharedMemorySize, colsw_lds<9>())
-                              : hipFuncSetAttribute(colsw_kernel<8>(dir, ring), hipFuncAttributeMaxDynamicSharedMemorySize, colsw_lds<8>());
+    for (uint32_t lg_l : {8u, 9u})
+        for (int dir : {FWD, INV})
+            if (e == hipSuccess) e = raise_lds_limit(colsw_launch(dir, lg_l));
     return e;
+}
+
+hipError_t setup_cols32_kernels()
+{
+    hipError_t e = raise_lds_limit(cols32_launch(FWD, 11));
+    return e == hipSuccess ? raise_lds_limit(cols32_launch(INV, 11)) : e;
 }
 
 // n = 2^lg_l * pitch <= 2^28 per transform; tw = half table of W_{2^lg_l}, (tw_lo, tw_hi) = two-level table of W_n.
 // tile_ring: tile-contiguous output [tile][k1][CW] (read back by k_rows32 with in_cw = CW), else the matrix layout.
-hipError_t launch_colsw(int dir, uint32_t lg_l, bool out_is_ring, bool tile_ring, const v2f *in, v2f *out, const v2f *tw,
-                        const v2f *tw_lo, const v2f *tw_hi, uint32_t pitch, uint64_t in_sb, uint64_t out_sb,
-                        uint32_t n_transforms, uint32_t xcd_swizzle, hipStream_t st)
+hipError_t launch_colsw(int dir, uint32_t lg_l, bool tile_ring, const v2f *in, v2f *out, const v2f *tw, const v2f *tw_lo,
+                        const v2f *tw_hi, uint32_t pitch, uint64_t in_sb, uint64_t out_sb, uint32_t n_transforms,
+                        uint32_t xcd_swizzle, hipStream_t st)
 {
     if (n_transforms == 0) return hipSuccess;
-    if (!colsw_supported(lg_l)) return hipErrorInvalidValue;
+    const KernelLaunch k = colsw_launch(dir, lg_l);
+    if (!k.kernel) return hipErrorInvalidValue;
     const uint32_t cw = colsw_width(lg_l);
     if (pitch < cw || ((uint64_t)pitch << lg_l) > (1ull << 28) || (pitch & (pitch - 1))) return hipErrorInvalidValue;
     const uint64_t blocks = (uint64_t)n_transforms * (pitch / cw);
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    if (blocks % 8) xcd_swizzle = 0;
+    if (hipError_t e = check_grid(blocks, &xcd_swizzle); e != hipSuccess) return e;
     uint32_t out_sk = tile_ring ? cw * 8u : pitch * 8u;
     uint32_t out_st = tile_ring ? (cw * 8u) << lg_l : cw * 8u;
     void *args[] = {&in, &out, &tw, &tw_lo, &tw_hi, &pitch, &in_sb, &out_sb, &out_sk, &out_st, &xcd_swizzle};
-    return lg_l == 9 ? hipLaunchKernel(colsw_kernel<9>(dir, out_is_ring), dim3((uint32_t)blocks), dim3(512), args, colsw_lds<9>(), st)
-                     : hipLaunchKernel(colsw_kernel<8>(dir, out_is_ring), dim3((uint32_t)blocks), dim3(512), args, colsw_lds<8>(), st);
-}
-
-template <int LGN, int CW>
-static int cols32_lds() { return Rows32<LGN, CW>::LDS_BYTES + 32 * CW * 8; }
-template <int LGN, int CW>
-static const void *cols32_kernel(int dir, bool ring)
-{
-    return dir == FWD ? (ring ? reinterpret_cast<const void *>(&k_cols32<LGN, CW, FWD, AUX_SC1>) : reinterpret_cast<const void *>(&k_cols32<LGN, CW, FWD, AUX_NT>))
-                      : (ring ? reinterpret_cast<const void *>(&k_cols32<LGN, CW, INV, AUX_SC1>) : reinterpret_cast<const void *>(&k_cols32<LGN, CW, INV, AUX_NT>));
-}
-
-bool cols32_supported(uint32_t lg_l) { return lg_l == 11; }
-
-hipError_t prepare_cols32(uint32_t lg_l)
-{
-    hipError_t e = hipSuccess;
-    for (int dir : {FWD, INV})
-        for (bool ring : {true, false})
-            if (e == hipSuccess && lg_l == 11)
-                e = hipFuncSetAttribute(cols32_kernel<11, 16>(dir, ring), hipFuncAttributeMaxDynamicSharedMemorySize, cols32_lds<11, 16>());
-    return cols32_supported(lg_l) ? e : hipErrorInvalidValue;
+    return hipLaunchKernel(k.kernel, dim3((uint32_t)blocks), dim3(k.threads), args, k.lds, st);
 }
 
 // n = 2^lg_l * pitch <= 2^28 per transform; tw = half table of W_{2^lg_l}, (tw_lo, tw_hi) = two-level table of W_n
-hipError_t launch_cols32(int dir, uint32_t lg_l, bool out_is_ring, const v2f *in, v2f *out, const v2f *tw, const v2f *tw_lo,
-                         const v2f *tw_hi, uint32_t pitch, uint64_t in_sb, uint64_t out_sb, uint32_t n_transforms,
-                         uint32_t xcd_swizzle, hipStream_t st)
+hipError_t launch_cols32(int dir, uint32_t lg_l, const v2f *in, v2f *out, const v2f *tw, const v2f *tw_lo, const v2f *tw_hi,
+                         uint32_t pitch, uint64_t in_sb, uint64_t out_sb, uint32_t n_transforms, uint32_t xcd_swizzle,
+                         hipStream_t st)
 {
     if (n_transforms == 0) return hipSuccess;
-    if (!cols32_supported(lg_l)) return hipErrorInvalidValue;
+    const KernelLaunch k = cols32_launch(dir, lg_l);
+    if (!k.kernel) return hipErrorInvalidValue;
     const uint32_t cw = 16;
-    if (pitch < 16 || ((uint64_t)pitch << lg_l) > (1ull << 28) || (pitch & (pitch - 1))) return hipErrorInvalidValue;
+    if (pitch < cw || ((uint64_t)pitch << lg_l) > (1ull << 28) || (pitch & (pitch - 1))) return hipErrorInvalidValue;
     const uint64_t blocks = (uint64_t)n_transforms * (pitch / cw);
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    if (blocks % 8) xcd_swizzle = 0;
+    if (hipError_t e = check_grid(blocks, &xcd_swizzle); e != hipSuccess) return e;
     void *args[] = {&in, &out, &tw, &tw_lo, &tw_hi, &pitch, &in_sb, &out_sb, &xcd_swizzle};
-    return hipLaunchKernel(cols32_kernel<11, 16>(dir, out_is_ring), dim3((uint32_t)blocks), dim3(1024), args, cols32_lds<11, 16>(), st);
+    return hipLaunchKernel(k.kernel, dim3((uint32_t)blocks), dim3(k.threads), args, k.lds, st);
 }
 
 }  // namespace fwa

@@ -162,7 +162,7 @@ static hipError_t launch_small16_dir(const v2f *src, v2f *dst, const v2f *tw, ui
     const uint32_t wg = 256;
     const uint32_t xpw = wg / (n / 16);
     const uint64_t blocks = (batch + xpw - 1) / xpw;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    if (hipError_t e = check_grid(blocks); e != hipSuccess) return e;
     const size_t lds = (lg_n == 4 || (shfl && lg_n <= 7)) ? 0 : (size_t)xpw * (n + n / 16) * sizeof(v2f);
     const dim3 g((uint32_t)blocks), b(wg);
     switch (lg_n) {

@@ -4,10 +4,6 @@
 
 namespace fwa {
 
-const void *rows32_kernel_2048(int dir, uint32_t in_cw) { return rows32_kernel_of<11>(dir, in_cw); }
-const void *rows32_kernel_big(uint32_t lg_l, int dir, uint32_t in_cw)
-{
-    return lg_l == 11 ? rows32_kernel_2048(dir, in_cw) : rows32_kernel_4096(dir, in_cw);
-}
+template const void *rows32_kernel<11>(int dir, uint32_t in_cw);
 
 }  // namespace fwa

@@ -3,6 +3,6 @@
 
 namespace fwa {
 
-const void *rows32_kernel_4096(int dir, uint32_t in_cw) { return rows32_kernel_of<12>(dir, in_cw); }
+template const void *rows32_kernel<12>(int dir, uint32_t in_cw);
 
 }  // namespace fwa

@@ -90,7 +90,7 @@ hipError_t launch_scale(const v2f *a, v2f *b, uint64_t n_samples, float scale, h
 {
     if (n_samples == 0) return hipSuccess;
     const uint64_t blocks = (n_samples + 8191) / 8192;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    if (hipError_t e = check_grid(blocks); e != hipSuccess) return e;
     hipLaunchKernelGGL(k_scale, dim3((uint32_t)blocks), dim3(256), 0, st, a, b, n_samples, scale);
     return hipGetLastError();
 }
@@ -150,7 +150,7 @@ hipError_t launch_copy(const void *src, void *dst, uint64_t bytes, hipStream_t s
 {
     const uint64_t n_chunks = bytes / 65536, n_vec = bytes / 16;
     if (n_vec == 0) return hipSuccess;
-    if (n_chunks > 0x7fffffffull) return hipErrorInvalidValue;
+    if (hipError_t e = check_grid(n_chunks); e != hipSuccess) return e;
     if (n_chunks)
         hipLaunchKernelGGL(k_copy, dim3((uint32_t)n_chunks), dim3(256), 0, st, static_cast<const char *>(src),
                            static_cast<char *>(dst), n_chunks);

@@ -10,16 +10,16 @@ hipError_t launch_small32(int dir, const v2f *src, v2f *dst, const v2f *tw, uint
     if (batch == 0) return hipSuccess;
     uint32_t lg_n = 0;
     while ((1u << lg_n) < n) ++lg_n;
-#define FWA_S32(L)                                                                               \
-    case L:                                                                                      \
-        return dir == FWD ? launch_small32_n<L, FWD>(src, dst, tw, batch, scale, st)             \
-                          : launch_small32_n<L, INV>(src, dst, tw, batch, scale, st)
     switch (lg_n) {
-        FWA_S32(9); FWA_S32(10); FWA_S32(11); FWA_S32(12);
-        case 13: case 14: case 15: return launch_small32_big(dir, lg_n, src, dst, tw, batch, scale, st);
+        case 9: return launch_small32_n<9>(dir, src, dst, tw, batch, scale, st);
+        case 10: return launch_small32_n<10>(dir, src, dst, tw, batch, scale, st);
+        case 11: return launch_small32_n<11>(dir, src, dst, tw, batch, scale, st);
+        case 12: return launch_small32_n<12>(dir, src, dst, tw, batch, scale, st);
+        case 13: return launch_small32_n<13>(dir, src, dst, tw, batch, scale, st);
+        case 14: return launch_small32_n<14>(dir, src, dst, tw, batch, scale, st);
+        case 15: return launch_small32_n<15>(dir, src, dst, tw, batch, scale, st);
         default: return hipErrorInvalidValue;
     }
-#undef FWA_S32
 }
 
 }  // namespace fwa

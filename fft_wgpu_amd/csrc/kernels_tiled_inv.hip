@@ -4,9 +4,6 @@
 
 namespace fwa {
 
-const void *tile_kernel_inv(int mode, uint32_t lg_l, bool buf, int role)
-{
-    return mode == TILE_COLS ? tile_kernel_m<16, INV, TILE_COLS>(lg_l, buf, role) : tile_kernel_m<16, INV, TILE_ROWS_T>(lg_l, buf, role);
-}
+template const void *tile_kernel<INV>(int mode, uint32_t lg_l, bool buf, int role);
 
 }  // namespace fwa

@@ -64,8 +64,37 @@ int64_t choose_path(uint32_t n, uint64_t batch, uint32_t lf[3], bool *colsw)
     return PATH_R2_GLOBAL;
 }
 
-// tile width (FFTs per workgroup) of pass i of the tiled path
-uint32_t pass_cw(const fwa_plan *, uint32_t) { return 16u; }
+// Kernel families, bit i set up by kFamilySetups[i]: each raises the dynamic-LDS limits of its kernels (kernels.h), once per
+// context, before the first plan that may launch one of them -- and only then: a plan of n <= 4096 loads no k_small32<14 / 15>.
+enum : uint32_t { FAM_SMALL32 = 1, FAM_1M = 2, FAM_ROWS32 = 4, FAM_COLSW = 8, FAM_COLS32 = 16, FAM_TILE = 32, FAM_LAB_RING = 64 };
+static hipError_t (*const kFamilySetups[])() = {
+    fwa::setup_small32_kernels, fwa::setup_1m_kernels, fwa::setup_rows32_kernels, fwa::setup_colsw_kernels,
+    fwa::setup_cols32_kernels, fwa::setup_tile_kernels,
+#ifdef FWA_LAB
+    fwa::setup_lab_1m_kernels,
+#endif
+};
+
+// The families a plan may launch on its path.  A tiled plan counts every pass-A and pass-C alternative that the keys "colsw",
+// "rows32", "p1_gen" and "tile_ring" can select without a new setup ("factors" and "path" run setup_path again).
+static uint32_t path_families(const fwa_plan *p)
+{
+    switch (p->path) {
+        case PATH_SMALL: return p->n > 4096 ? FAM_SMALL32 : 0u;
+        case PATH_TWOPASS_1M: return FAM_1M;
+        case PATH_RING_1M: return FAM_LAB_RING;
+        case PATH_TILED: {
+            uint32_t f = 0;
+            if (fwa::colsw_supported(p->lf[0])) f |= FAM_COLSW;
+            if (fwa::cols32_supported(p->lf[0])) f |= FAM_COLS32;
+            if (p->lf[0] == 10) f |= FAM_1M;  // k_p1_gen
+            if (!p->lf[2] && fwa::rows32_supported(p->lf[1])) f |= FAM_ROWS32;
+            if (std::min(p->lf[0], p->lf[1]) <= 10) f |= FAM_TILE;  // 2048 / 4096-point passes: k_cols32 / k_rows32 only
+            return f;
+        }
+        default: return 0u;
+    }
+}
 
 // Everything a plan needs for its path: kernel attributes (once per context), twiddle tables (shared through the
 // context's plan cache) and, on the pipelined paths, the ring + internal streams with the default geometry.
@@ -82,40 +111,12 @@ int32_t setup_path(fwa_plan *p)
 {
     fwa_ctx *ctx = p->ctx;
     const uint32_t fft_len = p->n;
-    if (p->path == PATH_SMALL && fft_len > 4096 && !ctx->setup_small_done) {
-        hipError_t e = fwa::setup_small_kernels();
+    const uint32_t todo = path_families(p) & ~ctx->kernel_families;
+    for (uint32_t i = 0; i < std::size(kFamilySetups); ++i) {
+        if (!((todo >> i) & 1u)) continue;
+        hipError_t e = kFamilySetups[i]();
         if (e != hipSuccess) return fail_hip(ctx, e, "hipFuncSetAttribute(max dynamic LDS)");
-        ctx->setup_small_done = true;
-    }
-    if ((p->path == PATH_TWOPASS_1M || p->path == PATH_RING_1M || (p->path == PATH_TILED && p->lf[0] == 10))
-        && !ctx->setup_1m_done) {
-        hipError_t e = fwa::setup_1m_kernels();
-#ifdef FWA_LAB
-        if (e == hipSuccess) e = fwa::setup_lab_1m_kernels();
-#endif
-        if (e != hipSuccess) return fail_hip(ctx, e, "hipFuncSetAttribute(max dynamic LDS)");
-        ctx->setup_1m_done = true;
-    }
-    if (p->path == PATH_TILED) {
-        const uint32_t nf = p->lf[2] ? 3 : 2;
-        for (uint32_t i = 0; i < nf; ++i)
-        {
-            if (nf == 2 && i == 1 && fwa::rows32_supported(p->lf[1])) {
-                hipError_t re = fwa::prepare_rows32(p->lf[1]);
-                if (re != hipSuccess) return fail_hip(ctx, re, "hipFuncSetAttribute(max dynamic LDS)");
-            }
-            if (i == 0 && fwa::cols32_supported(p->lf[0])) {
-                hipError_t ce = fwa::prepare_cols32(p->lf[0]);
-                if (ce != hipSuccess) return fail_hip(ctx, ce, "hipFuncSetAttribute(max dynamic LDS)");
-            }
-            if (i == 0 && fwa::colsw_supported(p->lf[0])) {
-                hipError_t ce = fwa::prepare_colsw(p->lf[0]);
-                if (ce != hipSuccess) return fail_hip(ctx, ce, "hipFuncSetAttribute(max dynamic LDS)");
-            }
-            if (p->lf[i] > 10) continue;  // 2048 / 4096-point passes: k_cols32 / k_rows32 only
-            hipError_t pe = fwa::prepare_tile(p->lf[i], 16);
-            if (pe != hipSuccess) return fail_hip(ctx, pe, "hipFuncSetAttribute(max dynamic LDS)");
-        }
+        ctx->kernel_families |= 1u << i;
     }
     // tables: shared by every plan of this (length, path, factorisation) on the context
     const uint32_t sig = p->lf[0] | (p->lf[1] << 8) | (p->lf[2] << 16);
@@ -253,11 +254,10 @@ struct TiledPass {
     {
         switch (kernel) {
             case COLSW:
-                return fwa::launch_colsw(dir, lg_l, true, ring_cw != 0, in, out, tw, tw_lo, tw_hi, pitch, sb, sb,
-                                         (uint32_t)cnt, swizzle, s);
+                return fwa::launch_colsw(dir, lg_l, ring_cw != 0, in, out, tw, tw_lo, tw_hi, pitch, sb, sb, (uint32_t)cnt,
+                                         swizzle, s);
             case COLS32:
-                return fwa::launch_cols32(dir, lg_l, true, in, out, tw, tw_lo, tw_hi, pitch, sb, sb, (uint32_t)cnt,
-                                          swizzle, s);
+                return fwa::launch_cols32(dir, lg_l, in, out, tw, tw_lo, tw_hi, pitch, sb, sb, (uint32_t)cnt, swizzle, s);
             case P1_GEN:
                 return fwa::launch_p1_gen(dir, true, in, out, tw, tw_lo, tw_hi, pitch, sb, sb, (uint32_t)cnt, swizzle, s);
             case ROWS32:
@@ -308,7 +308,7 @@ static TiledPass pass_a(const fwa_plan *p, const TiledShape &sh, const Tables &t
             ps.tw = tb.tw_inner;
             break;
         case TiledPass::TILE_COLS_K: {
-            const uint32_t cw = pass_cw(p, 0);
+            const uint32_t cw = fwa::TILE_CW;
             fwa::TileArgs &t = ps.ta;
             t.tw = tb.tw_l[0]; t.tw_lo = tb.tw_lo1; t.tw_hi = tb.tw_hi1;
             t.scale = 1.0f; t.cw = cw; t.role = fwa::ROLE_FIRST; t.xcd_swizzle = sh.swizzle;
@@ -328,7 +328,7 @@ static TiledPass pass_b(const fwa_plan *p, const TiledShape &sh, const Tables &t
     if (!sh.three) return ps;   // kernel == NONE
     ps.kernel = TiledPass::TILE_COLS_K;
     ps.dir = dir; ps.lg_l = p->lf[1];
-    const uint32_t cw = pass_cw(p, 1);
+    const uint32_t cw = fwa::TILE_CW;
     fwa::TileArgs &t = ps.ta;
     t.tw = tb.tw_l[1]; t.tw_lo = tb.tw_lo_b; t.tw_hi = tb.tw_hi_b;
     t.scale = 1.0f; t.cw = cw; t.role = fwa::ROLE_MIDDLE; t.xcd_swizzle = sh.swizzle;
@@ -349,7 +349,7 @@ static TiledPass pass_c(const fwa_plan *p, const TiledShape &sh, const Tables &t
     ps.kernel = rows32 ? TiledPass::ROWS32 : TiledPass::TILE_ROWS_K;
     switch (ps.kernel) {
         case TiledPass::TILE_ROWS_K: {
-            const uint32_t cw = pass_cw(p, li);
+            const uint32_t cw = fwa::TILE_CW;
             fwa::TileArgs &t = ps.ta;
             t.tw = tb.tw_l[li]; t.tw_lo = nullptr; t.tw_hi = nullptr;
             t.scale = scale; t.cw = cw; t.role = fwa::ROLE_LAST; t.xcd_swizzle = sh.swizzle;

@@ -171,22 +171,25 @@ __global__ __launch_bounds__((RW << (LGN - 5)), 4) void k_rows32(const v2f *__re
     FWA_STAMP_B(3);
 }
 
-// kernel entry points by row length; lg_l = 11, 12 live in kernels_rows32b.hip
-const void *rows32_kernel_small(uint32_t lg_l, int dir, uint32_t in_cw);
-const void *rows32_kernel_big(uint32_t lg_l, int dir, uint32_t in_cw);
-const void *rows32_kernel_4096(int dir, uint32_t in_cw);  // kernels_rows32c.hip
-
-template <int LGN, int DIR, int IN_CW>
-static const void *rows32_kernel() { return reinterpret_cast<const void *>(&k_rows32<LGN, DIR, rows32_rows(LGN), IN_CW>); }
+// k_rows32 of one row length by direction and ring input width (in_cw = 0: matrix input).  The 2048- and 4096-point rows are
+// instantiated in translation units of their own (kernels_rows32b.hip, kernels_rows32c.hip) so that the library builds in
+// parallel.
 template <int LGN>
-static const void *rows32_kernel_of(int dir, uint32_t in_cw)
+const void *rows32_kernel(int dir, uint32_t in_cw)
 {
-    if constexpr (LGN >= 10) {
-        if (in_cw == 32) return dir == FWD ? rows32_kernel<LGN, FWD, 32>() : rows32_kernel<LGN, INV, 32>();
-        if constexpr (LGN >= 11)
-            if (in_cw == 64) return dir == FWD ? rows32_kernel<LGN, FWD, 64>() : rows32_kernel<LGN, INV, 64>();
-    }
-    return dir == FWD ? rows32_kernel<LGN, FWD, 0>() : rows32_kernel<LGN, INV, 0>();
+    constexpr int RW = rows32_rows(LGN);
+    if constexpr (LGN >= 10)
+        if (in_cw == 32)
+            return dir == FWD ? reinterpret_cast<const void *>(&k_rows32<LGN, FWD, RW, 32>)
+                              : reinterpret_cast<const void *>(&k_rows32<LGN, INV, RW, 32>);
+    if constexpr (LGN >= 11)
+        if (in_cw == 64)
+            return dir == FWD ? reinterpret_cast<const void *>(&k_rows32<LGN, FWD, RW, 64>)
+                              : reinterpret_cast<const void *>(&k_rows32<LGN, INV, RW, 64>);
+    return dir == FWD ? reinterpret_cast<const void *>(&k_rows32<LGN, FWD, RW, 0>)
+                      : reinterpret_cast<const void *>(&k_rows32<LGN, INV, RW, 0>);
 }
+extern template const void *rows32_kernel<11>(int dir, uint32_t in_cw);
+extern template const void *rows32_kernel<12>(int dir, uint32_t in_cw);
 
 }  // namespace fwa

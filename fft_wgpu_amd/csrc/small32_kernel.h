@@ -146,24 +146,26 @@ __global__ __launch_bounds__((LGN <= 13 ? 256 : (1 << (LGN - 5))), 4) void k_sma
     small32_body<LGN, DIR, PREFETCH>(src, dst, tw, batch, scale, one_launch_block(), threadIdx.x);
 }
 
-static uint32_t small32_xpw(uint32_t lg_n) { return lg_n <= 13 ? 256u / (1u << (lg_n - 5)) : 1u; }  // lg_n >= 6
-static size_t small32_lds(uint32_t lg_n)
+constexpr uint32_t small32_xpw(uint32_t lg_n) { return lg_n <= 13 ? 256u / (1u << (lg_n - 5)) : 1u; }  // lg_n >= 6
+constexpr size_t small32_lds(uint32_t lg_n)
 {
     return (size_t)small32_xpw(lg_n) * ((size_t)(1u << lg_n) + (1u << (lg_n - 5))) * sizeof(float);
 }
-template <int LGN, int DIR>
-static hipError_t launch_small32_n(const v2f *src, v2f *dst, const v2f *tw, uint64_t batch, float scale, hipStream_t st)
+// n = 2^LGN; 8192 .. 32768 are instantiated in kernels_small32b.hip, a translation unit of its own so that the library builds
+// in parallel
+template <int LGN>
+hipError_t launch_small32_n(int dir, const v2f *src, v2f *dst, const v2f *tw, uint64_t batch, float scale, hipStream_t st)
 {
-    const uint32_t xpw = small32_xpw(LGN);
+    constexpr uint32_t xpw = small32_xpw(LGN);
     const uint64_t blocks = (batch + xpw - 1) / xpw;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_small32<LGN, DIR>), dim3((uint32_t)blocks), dim3(LGN <= 13 ? 256 : (1 << (LGN - 5))), small32_lds(LGN), st,
-                       src, dst, tw, batch, scale);
+    if (hipError_t e = check_grid(blocks); e != hipSuccess) return e;
+    const dim3 g((uint32_t)blocks), b(LGN <= 13 ? 256 : (1 << (LGN - 5)));
+    if (dir == FWD) hipLaunchKernelGGL((k_small32<LGN, FWD>), g, b, small32_lds(LGN), st, src, dst, tw, batch, scale);
+    else hipLaunchKernelGGL((k_small32<LGN, INV>), g, b, small32_lds(LGN), st, src, dst, tw, batch, scale);
     return hipGetLastError();
 }
-
-// n = 8192 .. 32768 (kernels_small32b.hip)
-hipError_t launch_small32_big(int dir, uint32_t lg_n, const v2f *src, v2f *dst, const v2f *tw, uint64_t batch, float scale,
-                              hipStream_t st);
+extern template hipError_t launch_small32_n<13>(int, const v2f *, v2f *, const v2f *, uint64_t, float, hipStream_t);
+extern template hipError_t launch_small32_n<14>(int, const v2f *, v2f *, const v2f *, uint64_t, float, hipStream_t);
+extern template hipError_t launch_small32_n<15>(int, const v2f *, v2f *, const v2f *, uint64_t, float, hipStream_t);
 
 }  // namespace fwa

@@ -25,33 +25,32 @@ __global__ __launch_bounds__(((1 << LGL) / 16) * CW) void k_tile(TileArgs a)
                                                    reinterpret_cast<v2f *>(smem), threadIdx.x);
 }
 
-template <int CW, int DIR, int MODE, bool BUF, int ROLE>
-static const void *tile_kernel_p(uint32_t lg_l)
+// k_tile of one direction by mode, length, buffer form and role: COLS passes come as first or middle pass, ROWS_T is always
+// the last; the 64-bit-pointer form (BUF = false, only above 4-GiB tiles) has no policy bits.  The inverse direction is
+// instantiated in kernels_tiled_inv.hip, a translation unit of its own so that the library builds in parallel.
+template <int DIR>
+const void *tile_kernel(int mode, uint32_t lg_l, bool buf, int role)
 {
-    switch (lg_l) {
-        case 6: return reinterpret_cast<const void *>(&k_tile<6, CW, DIR, MODE, BUF, ROLE>);
-        case 7: return reinterpret_cast<const void *>(&k_tile<7, CW, DIR, MODE, BUF, ROLE>);
-        case 8: return reinterpret_cast<const void *>(&k_tile<8, CW, DIR, MODE, BUF, ROLE>);
-        case 9: return reinterpret_cast<const void *>(&k_tile<9, CW, DIR, MODE, BUF, ROLE>);
-        case 10: return reinterpret_cast<const void *>(&k_tile<10, CW, DIR, MODE, BUF, ROLE>);
-        default: return nullptr;
-    }
+    auto of = [lg_l](auto mode_, auto buf_, auto role_) -> const void * {
+        constexpr int M = decltype(mode_)::value, R = decltype(role_)::value;
+        constexpr bool B = decltype(buf_)::value;
+        switch (lg_l) {
+            case 6: return reinterpret_cast<const void *>(&k_tile<6, TILE_CW, DIR, M, B, R>);
+            case 7: return reinterpret_cast<const void *>(&k_tile<7, TILE_CW, DIR, M, B, R>);
+            case 8: return reinterpret_cast<const void *>(&k_tile<8, TILE_CW, DIR, M, B, R>);
+            case 9: return reinterpret_cast<const void *>(&k_tile<9, TILE_CW, DIR, M, B, R>);
+            case 10: return reinterpret_cast<const void *>(&k_tile<10, TILE_CW, DIR, M, B, R>);
+            default: return nullptr;
+        }
+    };
+    using COLS = std::integral_constant<int, TILE_COLS>;
+    using ROWS_T = std::integral_constant<int, TILE_ROWS_T>;
+    using NO_ROLE = std::integral_constant<int, 0>;
+    if (!buf) return mode == TILE_COLS ? of(COLS{}, std::false_type{}, NO_ROLE{}) : of(ROWS_T{}, std::false_type{}, NO_ROLE{});
+    if (mode != TILE_COLS) return of(ROWS_T{}, std::true_type{}, std::integral_constant<int, ROLE_LAST>{});
+    return role == ROLE_MIDDLE ? of(COLS{}, std::true_type{}, std::integral_constant<int, ROLE_MIDDLE>{})
+                               : of(COLS{}, std::true_type{}, std::integral_constant<int, ROLE_FIRST>{});
 }
-// COLS passes come as first or middle pass, ROWS_T is always the last; the 64-bit-pointer form (BUF = false,
-// only above 4-GiB tiles) has no policy bits.
-template <int CW, int DIR, int MODE>
-static const void *tile_kernel_m(uint32_t lg_l, bool buf, int role)
-{
-    if (!buf) return tile_kernel_p<CW, DIR, MODE, false, 0>(lg_l);
-    if constexpr (MODE == TILE_COLS) {
-        if (role == ROLE_MIDDLE) return tile_kernel_p<CW, DIR, MODE, true, ROLE_MIDDLE>(lg_l);
-        return tile_kernel_p<CW, DIR, MODE, true, ROLE_FIRST>(lg_l);
-    } else {
-        return tile_kernel_p<CW, DIR, MODE, true, ROLE_LAST>(lg_l);
-    }
-}
-// entry points of one direction (dir = FWD: kernels_tiled.hip, INV: kernels_tiled_inv.hip)
-const void *tile_kernel_fwd(int mode, uint32_t lg_l, bool buf, int role);
-const void *tile_kernel_inv(int mode, uint32_t lg_l, bool buf, int role);
+extern template const void *tile_kernel<INV>(int mode, uint32_t lg_l, bool buf, int role);
 
 }  // namespace fwa
