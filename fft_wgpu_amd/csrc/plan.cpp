@@ -433,8 +433,13 @@ int32_t fwa_plan_create(fwa_ctx *ctx, int32_t kind, uint32_t fft_len, fwa_buf *s
         return fail(ctx, FWA_ERR_INVALID_ARG, "this plan kind owns its second buffer; pass NULL");
     if (src2_or_null && src2_or_null->bytes != src->bytes)
         return fail(ctx, FWA_ERR_INVALID_ARG, "second buffer must have the size of the first");
-    if (src2_or_null && src2_or_null->p == src->p && src->bytes)
-        return fail(ctx, FWA_ERR_INVALID_ARG, "the two buffers must be distinct");
+    if (src2_or_null && src->bytes) {
+        // [p, p + bytes) of the two buffers: the same memory twice, or two views of one allocation that share a part
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(src->p), b0 = reinterpret_cast<uintptr_t>(src2_or_null->p);
+        if (a0 == b0) return fail(ctx, FWA_ERR_INVALID_ARG, "the two buffers must be distinct");
+        if (a0 < b0 + src2_or_null->bytes && b0 < a0 + src->bytes)
+            return fail(ctx, FWA_ERR_INVALID_ARG, "the two buffers must not overlap");
+    }
     if (reinterpret_cast<uintptr_t>(src->p) & 15)
         return fail(ctx, FWA_ERR_INVALID_ARG, "buffer must be 16-byte aligned");
 

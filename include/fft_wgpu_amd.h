@@ -119,7 +119,12 @@ int32_t fwa_stream_destroy(fwa_stream *stream);
 /* ---- buffers : replaces create_buffer / write_buffer / copy_buffer_to_buffer /
  *                map_async+get_mapped_range (examples/basic.rs:50-64,73,84-90,105-122) */
 int32_t fwa_buf_alloc(fwa_ctx *ctx, uint64_t bytes, fwa_buf **out);
-/* Zero-copy interop: wrap device memory owned by someone else (never freed by fwa_buf_free). */
+/* Zero-copy interop: wrap device memory owned by someone else (never freed by fwa_buf_free), e.g. a slice of a
+ * tensor or of the caller's own arena.  16-byte alignment of device_ptr is the only placement requirement
+ * (FWA_ERR_INVALID_ARG otherwise): the view may start anywhere inside an allocation and may cross any address
+ * boundary.  A plan reads and writes only [device_ptr, device_ptr + bytes) of the buffers it was created on (plus
+ * its own scratch), and fwa_calib_copy / fwa_fill_synthetic / fwa_buf_copy only the ranges they are given: the
+ * bytes on either side of a view are never touched (tests/test_gpu_containment.py). */
 int32_t fwa_buf_wrap(fwa_ctx *ctx, void *device_ptr, uint64_t bytes, fwa_buf **out);
 int32_t fwa_buf_free(fwa_buf *buf);
 int32_t fwa_buf_upload(fwa_buf *dst, uint64_t dst_offset, const void *host, uint64_t bytes,
@@ -155,7 +160,8 @@ uint64_t fwa_buf_size(const fwa_buf *buf);
  *   Normalize::new(&device,&queue,&buffer1,&buffer2,fft_len) processor.rs:422-428 (src2 required)
  * batch is implicit: fwa_buf_size(src) / 8 / fft_len.  Buffers stay caller-owned and must
  * outlive the plan.  Rejected with FWA_ERR_INVALID_ARG: fft_len not a power of two (or 0),
- * size(src) % (8*fft_len) != 0, size(src2) != size(src), missing/extra src2.
+ * size(src) % (8*fft_len) != 0, size(src2) != size(src), missing/extra src2, src2 the same as or
+ * overlapping src ([ptr, ptr + size) of the two must be disjoint), src not 16-byte aligned.
  *
  * fwa_plan_exec mirrors X::proc(&self, &mut encoder) -> &wgpu::Buffer
  * (processor.rs:110,293,467,622): asynchronous and stream-ordered, allocates nothing, and
