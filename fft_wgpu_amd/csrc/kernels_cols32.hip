@@ -23,7 +23,8 @@ __global__ __launch_bounds__(1024, 4) void k_cols32(const v2f *__restrict__ in, 
 {
     using G = Rows32<LGN, CW>;
     static_assert(G::WG == 1024 && (CW == 8 || CW == 16), "1024 threads");
-    constexpr int N = G::N, T = G::T, PNS = G::PNS, J2 = 1024, R2 = N / 1024, B2 = 32 / R2;
+    constexpr int N = G::N, T = G::T, PNS = G::PNS, J2 = G::J2, B2 = G::B2;
+    static_assert(G::R1 == 32 && !G::TWO, "32 x 32 x R2");
     constexpr int LGCW = CW == 8 ? 3 : 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *lds = reinterpret_cast<float *>(smem);
@@ -52,44 +53,20 @@ __global__ __launch_bounds__(1024, 4) void k_cols32(const v2f *__restrict__ in, 
     }
     const v2f A = look(col * kk);
 
-    auto exchange = [&](v2f (&v)[32], uint32_t wbase, auto woff, uint32_t rbase, auto roff) {
-        static_for<0, 32>([&](auto r_) { constexpr int i = decltype(r_)::value; lf[wbase + woff(r_)] = v[i].x; });
-        __syncthreads();
-        static_for<0, 32>([&](auto r_) { constexpr int i = decltype(r_)::value; v[i].x = lf[rbase + roff(r_)]; });
-        __syncthreads();
-        static_for<0, 32>([&](auto r_) { constexpr int i = decltype(r_)::value; lf[wbase + woff(r_)] = v[i].y; });
-        __syncthreads();
-        static_for<0, 32>([&](auto r_) { constexpr int i = decltype(r_)::value; v[i].y = lf[rbase + roff(r_)]; });
-    };
-    constexpr auto P = [](uint32_t p) constexpr { return p + (p >> 5); };
     const uint32_t k_hi = kk >> 5, k_lo = kk & 31;
     const uint32_t rbase = kk + k_hi;
 
     fft_reg<32, DIR>(x);
     twiddle_outputs<32, N, DIR>(x, tw, kk);   // look-ups at the point of use: prefetched they spill here (- 6 % at 2^23)
-    exchange(x, 33 * kk, [](auto r_) { return (uint32_t)brev<32>(decltype(r_)::value); }, rbase, [&](auto i_) {
-        constexpr uint32_t i = decltype(i_)::value;
-        return P(i * (N / 32));
-    });
-    fft_reg<32, DIR>(x);
+    exchange32<G::ex1_w, G::ex1_r>(x, lf, 33 * kk, lf, rbase);
+    fft_reg<32, DIR>(x);   // stage 1 with B1 = 1, spelled out: through stage1() the instruction order changes
     twiddle_outputs<32, N, DIR>(x, tw, kk & ~31u);
     __syncthreads();
-    exchange(x, (kk - k_lo) * 32 + k_lo + k_hi * 32, [&](auto i_) {
-        constexpr uint32_t i = decltype(i_)::value;
-        return P((uint32_t)brev<32>(i) * 32);
-    }, rbase, [&](auto i_) {
-        constexpr uint32_t i = decltype(i_)::value;
-        return P((i / R2) * T + (i % R2) * (N / R2));
-    });
-    static_for<0, B2>([&](auto b_) {
-        constexpr int b = decltype(b_)::value;
-        v2f(&z)[R2] = *reinterpret_cast<v2f(*)[R2]>(&x[b * R2]);
-        fft_reg<R2, DIR>(z);
-        static_for<0, R2>([&](auto q_) {
-            constexpr int q = decltype(q_)::value;
-            const v2f w = cmul(A, two[(q * B2 + b) * CW + c]);
-            buf_store<AUX_OUT>(cmul_tw<DIR>(z[brev<R2>(q)], w), rout, voff, soff + (b * T + q * J2) * rstep);
-        });
+    exchange32<G::ex2_w, G::ex2_r>(x, lf, (kk - k_lo) * G::R1 + k_lo + k_hi * G::R1, lf, rbase);
+    last_stage<G::R2, DIR>(x, [&](auto b_, auto q_, const v2f &v) {
+        constexpr int b = decltype(b_)::value, q = decltype(q_)::value;
+        const v2f w = cmul(A, two[(q * B2 + b) * CW + c]);
+        buf_store<AUX_OUT>(cmul_tw<DIR>(v, w), rout, voff, soff + (b * T + q * J2) * rstep);
     });
 }
 
@@ -112,7 +89,8 @@ __global__ __launch_bounds__(512, 4) void k_colsw(const v2f *__restrict__ in, v2
 {
     using G = Rows32<LGN, CW>;
     static_assert(G::WG == 512 && (LGN == 8 || LGN == 9), "512 threads: 512 x 32 or 256 x 64 columns");
-    constexpr int N = G::N, T = G::T, PNS = G::PNS, R1 = N / 32, B1 = 32 / R1;
+    constexpr int N = G::N, T = G::T, PNS = G::PNS, R1 = G::R1, B1 = G::B1;
+    static_assert(G::TWO && R1 == T, "32 x (N/32), one exchange");
     constexpr int LGCW = 14 - LGN;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *lds = reinterpret_cast<float *>(smem);
@@ -150,32 +128,17 @@ __global__ __launch_bounds__(512, 4) void k_colsw(const v2f *__restrict__ in, v2
     fft_reg<32, DIR>(x);
     if constexpr (PF & 5) twiddle_apply<32, N, DIR>(x, w0);
     else twiddle_outputs<32, N, DIR>(x, tw, kk);
-    constexpr auto P = [](uint32_t p) constexpr { return p + (p >> 5); };
-    auto wpos = [](auto r_) { return (uint32_t)brev<32>(decltype(r_)::value); };
-    auto rpos = [&](auto i_) { constexpr uint32_t i = decltype(i_)::value; return P((i / R1) * T + (i % R1) * 32); };
-    static_for<0, 32>([&](auto r_) { constexpr int i = decltype(r_)::value; lf[33 * kk + wpos(r_)] = x[i].x; });
-    __syncthreads();
-    static_for<0, 32>([&](auto r_) { constexpr int i = decltype(r_)::value; x[i].x = lf[kk + rpos(r_)]; });
-    __syncthreads();
-    static_for<0, 32>([&](auto r_) { constexpr int i = decltype(r_)::value; lf[33 * kk + wpos(r_)] = x[i].y; });
-    __syncthreads();
-    static_for<0, 32>([&](auto r_) { constexpr int i = decltype(r_)::value; x[i].y = lf[kk + rpos(r_)]; });
+    exchange32<G::ex1_w, G::ex1_r>(x, lf, 33 * kk, lf, kk);  // P(kk) = kk: kk < T <= 16
 
     const uint32_t voff_o = kk * out_sk + c * 8;
     const uint32_t soff_o = tile * out_st;
     FWA_STAMP(2);
-    static_for<0, B1>([&](auto b_) {
-        constexpr int b = decltype(b_)::value;
-        v2f(&z)[R1] = *reinterpret_cast<v2f(*)[R1]>(&x[b * R1]);
-        fft_reg<R1, DIR>(z);
-        v2f ab = A;
-        if constexpr (b != 0) ab = cmul(A, tb[b * CW + c]);
-        static_for<0, R1>([&](auto q_) {
-            constexpr int q = decltype(q_)::value;
-            v2f w = ab;
-            if constexpr (q != 0) w = cmul(ab, tq[q * CW + c]);
-            buf_store<AUX_OUT>(cmul_tw<DIR>(z[brev<R1>(q)], w), rout, voff_o, soff_o + (b * T + q * 32) * out_sk);
-        });
+    last_stage<R1, DIR>(x, [&](auto b_, auto q_, const v2f &v) {
+        constexpr int b = decltype(b_)::value, q = decltype(q_)::value;
+        v2f w = A;
+        if constexpr (b != 0) w = cmul(w, tb[b * CW + c]);
+        if constexpr (q != 0) w = cmul(w, tq[q * CW + c]);
+        buf_store<AUX_OUT>(cmul_tw<DIR>(v, w), rout, voff_o, soff_o + (b * T + q * 32) * out_sk);
     });
     FWA_STAMP(3);
 }

@@ -32,9 +32,10 @@ namespace fwa {
 // pass of the 2^19 plan, and 2048-point rows did not exist: 2^21 needed three passes.)
 // ---------------------------------------------------------------------------
 template <int LGN, int RW = 16>
-struct Rows32 {
-    static constexpr int N = 1 << LGN, T = N / 32, WG = RW * T;
-    static constexpr int PN = N + N / 32;
+struct Rows32 : Net32<LGN> {
+    using Net32<LGN>::T;
+    using Net32<LGN>::PN;
+    static constexpr int WG = RW * T;
     // Padded floats per row.  In the transposed role a 32-lane group of a ds_read_b32 / ds_write_b32 holds RW adjacent
     // rows x 32/RW adjacent positions: with a row skew of 32/RW floats (mod 32) the RW x 32/RW addresses fall on 32
     // different banks (RW = 8: 4, RW = 16: 2); from 32 rows on, any odd skew does.  (Round 2 used 17 for every RW: one
@@ -61,11 +62,6 @@ __global__ __launch_bounds__((RW << (LGN - 5)), 4) void k_rows32(const v2f *__re
     using G = Rows32<LGN, RW>;
     constexpr int N = G::N, T = G::T, PNS = G::PNS;
     constexpr int LGRW = RW == 8 ? 3 : 4;
-    constexpr int R1 = (LGN == 9) ? 16 : 32;
-    constexpr bool TWO = (32 * R1 == N);
-    constexpr int R2 = TWO ? 1 : N / (32 * R1);
-    constexpr int B1 = 32 / R1;
-    constexpr int J2 = 32 * R1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *lds = reinterpret_cast<float *>(smem);
     const uint32_t tid = threadIdx.x;
@@ -75,9 +71,8 @@ __global__ __launch_bounds__((RW << (LGN - 5)), 4) void k_rows32(const v2f *__re
     const uint64_t bt = bid / tiles;
     const uint32_t xf = tid / T, t = tid % T;  // loading role: row, butterfly
     const uint32_t r = tid & (RW - 1), kk = tid >> LGRW;  // storing role
-    float *lfw = lds + xf * PNS;
-    const float *lfr_same = lfw;
-    const float *lfr_t = lds + r * PNS;
+    float *lfw = lds + xf * PNS;         // the row this lane loaded
+    const float *lfr_t = lds + r * PNS;  // the row it stores
     static_assert(IN_CW == 0 || (T % IN_CW == 0), "a load instruction covers whole column tiles");
     const __amdgpu_buffer_rsrc_t rin =
         IN_CW ? __builtin_amdgcn_make_buffer_rsrc(const_cast<v2f *>(in + bt * in_sb), 0, n1 * (N * 8u), 0x00020000)
@@ -87,32 +82,20 @@ __global__ __launch_bounds__((RW << (LGN - 5)), 4) void k_rows32(const v2f *__re
     const uint32_t voff = IN_CW ? (((t / (IN_CW ? IN_CW : 1)) * n1 + tile * RW + xf) * (uint32_t)IN_CW + (t % (IN_CW ? IN_CW : 1))) * 8 : (xf * N + t) * 8;
     const uint32_t mstep = IN_CW ? n1 * (T * 8u) : T * 8u;  // bytes between samples n2 and n2 + T of a row
 
-    auto exchange = [&](v2f (&x)[32], float *wp, uint32_t wbase, auto woff, const float *rp, uint32_t rbase, auto roff) {
-        static_for<0, 32>([&](auto r_) { constexpr int i = decltype(r_)::value; wp[wbase + woff(r_)] = x[i].x; });
-        __syncthreads();
-        static_for<0, 32>([&](auto r_) { constexpr int i = decltype(r_)::value; x[i].x = rp[rbase + roff(r_)]; });
-        __syncthreads();
-        static_for<0, 32>([&](auto r_) { constexpr int i = decltype(r_)::value; wp[wbase + woff(r_)] = x[i].y; });
-        __syncthreads();
-        static_for<0, 32>([&](auto r_) { constexpr int i = decltype(r_)::value; x[i].y = rp[rbase + roff(r_)]; });
-    };
-    constexpr auto P = [](uint32_t p) constexpr { return p + (p >> 5); };
     const uint32_t t_hi = t >> 5, t_lo = t & 31;
 
     constexpr int PF = LGN <= 10 ? FWA_PF_ROWS32 : 0;   // 512 / 1024-point rows (the 2^16 .. 2^19 plans)
     Twiddles<32, N> w0;
-    Twiddles<R1, N> w1[B1];
+    Stage1Twiddles<LGN> w1;
     if constexpr (PF & 1) twiddle_fetch<32, N>(w0, tw, t);
-    if constexpr (!TWO && (PF & 2))
-        static_for<0, B1>([&](auto b_) { constexpr int b = decltype(b_)::value; twiddle_fetch<R1, N>(w1[b], tw, (t + b * T) & ~31u); });
+    if constexpr (!G::TWO && (PF & 2)) stage1_fetch<LGN>(w1, tw, t);
     v2f x[32];
     FWA_ENTRY_HOOK();
     FWA_STAMP_B(0);
     static_for<0, 32>([&](auto m_) { constexpr int m = decltype(m_)::value; x[m] = buf_load<AUX_DEFAULT>(rin, voff, m * mstep); });
     FWA_STAMP_B(1);
     if constexpr (PF & 4) twiddle_fetch<32, N>(w0, tw, t);
-    if constexpr (!TWO && (PF & 8))
-        static_for<0, B1>([&](auto b_) { constexpr int b = decltype(b_)::value; twiddle_fetch<R1, N>(w1[b], tw, (t + b * T) & ~31u); });
+    if constexpr (!G::TWO && (PF & 8)) stage1_fetch<LGN>(w1, tw, t);
     fft_reg<32, DIR>(x);
     if constexpr (PF & 5) twiddle_apply<32, N, DIR>(x, w0);
     else twiddle_outputs<32, N, DIR>(x, tw, t);
@@ -120,54 +103,18 @@ __global__ __launch_bounds__((RW << (LGN - 5)), 4) void k_rows32(const v2f *__re
     const uint32_t voff_o = (kk * n1 + r) * 8;
     const uint32_t soff_o = tile * (RW * 8);
     const uint32_t kstep = n1 * 8;  // bytes per unit of K2
-    if constexpr (TWO) {
-        // -> last stage (radix R1, J = 32, s = 0) in the storing role: butterfly idx = kk + b*T of row r
-        exchange(x, lfw, 33 * t, [](auto r_) { return (uint32_t)brev<32>(decltype(r_)::value); }, lfr_t, kk + (kk >> 5), [&](auto i_) {
-            constexpr uint32_t i = decltype(i_)::value;
-            return P((i / R1) * T + (i % R1) * (N / R1));
-        });
-        static_for<0, B1>([&](auto b_) {
-            constexpr int b = decltype(b_)::value;
-            v2f(&z)[R1] = *reinterpret_cast<v2f(*)[R1]>(&x[b * R1]);
-            fft_reg<R1, DIR>(z);
-            static_for<0, R1>([&](auto q_) {
-                constexpr int q = decltype(q_)::value;
-                buf_store<AUX_NT>(z[brev<R1>(q)] * scale, rout, voff_o, soff_o + (b * T + q * 32) * kstep);
-            });
-        });
+    // the last stage runs in the storing role: butterfly idx = kk + b*T of row r
+    if constexpr (G::TWO) {
+        exchange32<G::ex1_w, G::ex1_r>(x, lfw, 33 * t, lfr_t, kk + (kk >> 5));
     } else {
-        exchange(x, lfw, 33 * t, [](auto r_) { return (uint32_t)brev<32>(decltype(r_)::value); }, lfr_same, t + t_hi, [&](auto i_) {
-            constexpr uint32_t i = decltype(i_)::value;
-            return P((i / R1) * T + (i % R1) * (N / R1));
-        });
-        static_for<0, B1>([&](auto b_) {
-            constexpr int b = decltype(b_)::value;
-            v2f(&z)[R1] = *reinterpret_cast<v2f(*)[R1]>(&x[b * R1]);
-            fft_reg<R1, DIR>(z);
-            const uint32_t idx = t + b * T, sJ = idx & ~31u;
-            if constexpr (PF & 10) twiddle_apply<R1, N, DIR>(z, w1[b]);
-            else twiddle_outputs<R1, N, DIR>(z, tw, sJ);
-        });
+        exchange32<G::ex1_w, G::ex1_r>(x, lfw, 33 * t, lfw, t + t_hi);
+        stage1<LGN, DIR, (PF & 10) != 0>(x, w1, tw, t);
         __syncthreads();
-        // -> last stage (radix R2, J = N/R2, s = 0) in the storing role: butterfly idx = kk + b*T of row r
-        constexpr int B2 = 32 / R2;
-        exchange(x, lfw, (t - t_lo) * R1 + t_lo + t_hi * R1, [&](auto i_) {
-            constexpr uint32_t i = decltype(i_)::value;
-            return P((i / R1) * T * R1 + (uint32_t)brev<R1>(i % R1) * 32);
-        }, lfr_t, kk + (kk >> 5), [&](auto i_) {
-            constexpr uint32_t i = decltype(i_)::value;
-            return P((i / R2) * T + (i % R2) * (N / R2));
-        });
-        static_for<0, B2>([&](auto b_) {
-            constexpr int b = decltype(b_)::value;
-            v2f(&z)[R2] = *reinterpret_cast<v2f(*)[R2]>(&x[b * R2]);
-            fft_reg<R2, DIR>(z);
-            static_for<0, R2>([&](auto q_) {
-                constexpr int q = decltype(q_)::value;
-                buf_store<AUX_NT>(z[brev<R2>(q)] * scale, rout, voff_o, soff_o + (b * T + q * J2) * kstep);
-            });
-        });
+        exchange32<G::ex2_w, G::ex2_r>(x, lfw, (t - t_lo) * G::R1 + t_lo + t_hi * G::R1, lfr_t, kk + (kk >> 5));
     }
+    last_stage<G::RL, DIR>(x, [&](auto b_, auto q_, const v2f &v) {
+        buf_store<AUX_NT>(v * scale, rout, voff_o, soff_o + (decltype(b_)::value * T + decltype(q_)::value * G::JL) * kstep);
+    });
     FWA_STAMP_B(3);
 }
 
