@@ -112,8 +112,8 @@ int32_t exchange(fwa_comm *c, const Piece *sends, size_t ns, const Piece *recvs,
     Rccl *r = nullptr;
     int32_t st = need_rccl(c->ctx, &r);
     if (st) return st;
-    if ((st = fwa_int::use_device(c->ctx))) return st;
-    hipStream_t hs = fwa_int::stream_raw(stream);
+    USE_DEVICE(c->ctx);
+    hipStream_t hs = fwa_int::raw(stream);
     ncclResult_t e = r->GroupStart();
     if (e != ncclSuccess) return fail_nccl(c->ctx, r, e, "ncclGroupStart");
     for (size_t i = 0; i < ns && e == ncclSuccess; ++i)
@@ -159,7 +159,7 @@ int32_t fwa_comm_create(fwa_ctx *ctx, const uint8_t id[FWA_COMM_ID_BYTES], int32
     Rccl *r = nullptr;
     int32_t st = need_rccl(ctx, &r);
     if (st) return st;
-    if ((st = fwa_int::use_device(ctx))) return st;
+    USE_DEVICE(ctx);
     fwa_comm *c = new (std::nothrow) fwa_comm;
     if (!c) return fwa_int::fail(ctx, FWA_ERR_OUT_OF_MEMORY, "host allocation failed");
     ncclUniqueId u;
@@ -185,7 +185,7 @@ int32_t fwa_comm_destroy(fwa_comm *comm)
     if (!comm) return FWA_OK;
     Rccl *r = rccl();
     if (comm->comm && r->CommDestroy) {
-        (void)fwa_int::use_device(comm->ctx);
+        (void)hipSetDevice(comm->ctx->device);
         (void)r->CommDestroy(comm->comm);
     }
     delete comm;
@@ -198,7 +198,7 @@ int32_t fwa_comm_get_i64(const fwa_comm *comm, const char *key, int64_t *value)
     const std::string k(key);
     if (k == "rank") *value = comm->rank;
     else if (k == "world") *value = comm->world;
-    else if (k == "device") *value = fwa_int::ctx_device(comm->ctx);
+    else if (k == "device") *value = comm->ctx->device;
     else return fwa_int::fail(comm->ctx, FWA_ERR_INVALID_ARG, "unknown key: " + k);
     return FWA_OK;
 }
@@ -219,7 +219,7 @@ int32_t fwa_comm_sendrecv(fwa_comm *comm, const fwa_buf *send, uint64_t send_off
     if ((send_to == comm->rank) != (recv_from == comm->rank) || (send_to == comm->rank && send_bytes != recv_bytes))
         return fwa_int::fail(ctx, FWA_ERR_INVALID_ARG,
                              "a send to this rank itself needs the matching receive in the same call");
-    if (stream && fwa_int::stream_ctx(stream) != ctx)
+    if (stream && stream->ctx != ctx)
         return fwa_int::fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to another context");
     const Piece s{send_to >= 0 ? at(send, send_offset) : nullptr, send_bytes, send_to};
     const Piece r{recv_from >= 0 ? at(recv, recv_offset) : nullptr, recv_bytes, recv_from};
@@ -269,7 +269,7 @@ int32_t move_slabs(fwa_comm *comm, bool gather, int32_t root, const fwa_buf *sla
         return fwa_int::fail(comm ? comm->ctx : nullptr, FWA_ERR_INVALID_ARG, "comm/slab is NULL or fft_len is 0");
     fwa_ctx *ctx = comm->ctx;
     if (root < 0 || root >= comm->world) return fwa_int::fail(ctx, FWA_ERR_INVALID_ARG, "root out of range");
-    if (stream && fwa_int::stream_ctx(stream) != ctx)
+    if (stream && stream->ctx != ctx)
         return fwa_int::fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to another context");
     const bool is_root = comm->rank == root;
     std::vector<uint64_t> off((size_t)(is_root ? comm->world : 1)), len(off.size());

@@ -4,7 +4,8 @@
 //   ctx_streams.cpp  contexts, error strings, device enumeration, the slab rule, streams (+ the overlap check), events
 //   buffers.cpp      device / pinned memory, uploads, downloads, copies (peer copies across contexts), synthetic data
 //   tables.cpp       twiddle tables (reference twiddle rule src/processor.rs:43-49), the ring pool, pipeline objects
-//   plan.cpp         path choice, plan create / destroy / exec (the four plan objects of src/processor.rs)
+//   schedule.h       path choice, kernel limits and the kernel of every pass of a tiled plan: pure integer logic, no HIP
+//   plan.cpp         plan create / destroy / exec (the four plan objects of src/processor.rs)
 //   tuning.cpp       fwa_plan_get_i64 / fwa_plan_set_i64
 //   comm.cpp         fwa_comm_*: slab movement over RCCL
 #pragma once
@@ -32,17 +33,6 @@ constexpr bool kLab = true;
 #else
 constexpr bool kLab = false;
 #endif
-
-enum fwa_path : int64_t {
-    PATH_SMALL = 0,       // n <= 32768: one launch (k_chunk / k_small32)
-    PATH_TWOPASS_1M = 1,  // n = 2^20: k_p1_1m + k_p2_1m per group of transforms
-    PATH_R2_GLOBAL = 2,   // the reference recurrence literally, one launch per stage (forced only)
-    PATH_NORMALIZE = 3,
-    PATH_IDENTITY = 4,    // n = 1
-    PATH_RING_1M = 5,     // n = 2^20: the same two passes as ONE persistent launch with a small ring (k_ring_1m)
-    // 8 was the L2-resident team path (k_team, rounds 2-5; removed in round 6: profiles/round6/lab_pruned_families.patch)
-    PATH_TILED = 7,       // n = N1*N2[*N3], each 64..1024: 2-3 k_tile passes
-};
 
 namespace fwa_int {
 
@@ -130,13 +120,9 @@ struct fwa_plan {
     uint64_t ring_bytes = 0;
     int64_t group = 16;            // transforms per launch
     int64_t n_streams = 2;         // internal streams (chains) the groups alternate over
-    // XCD-aware block -> tile mapping (xcd_map bits): -1 = per-path, per-size default (5 on the 2^20 two-pass path;
-    // tiled plans: tiled_swizzle_default, plan.cpp)
+    // XCD-aware block -> tile mapping (xcd_map bits): -1 = per-path, per-size default (swizzle_default, plan.cpp)
     int64_t xcd_swizzle = -1;
-    int64_t rows32 = 1;            // two-pass tiled plans with a 512..4096-point second factor: 1 = k_rows32 last
-    int64_t p1_gen = 1;            // tiled plans with first factor 1024: 1 = k_p1_gen as pass A, 0 = k_tile
-    int64_t colsw = 0;             // tiled plans with first factor 256 / 512: 1 = k_colsw (64 / 32-column tiles) first
-    int64_t tile_ring = 1;         // k_colsw + k_rows32: 1 = tile-contiguous ring slab, 0 = matrix layout
+    fwa_int::TiledFlags flags;     // tiled plans: the keys "colsw", "rows32", "p1_gen", "tile_ring" (schedule.h)
     // laboratory: the ring is this many times larger and the groups rotate through it (same launches, larger cache
     // footprint: prices what the Infinity Cache gives the ring)
     int64_t ring_rotate = 1;
@@ -180,12 +166,6 @@ const char *thread_error_string();
     } while (0)
 
 inline bool is_pow2(uint32_t n) { return n && !(n & (n - 1)); }
-inline uint32_t ilog2(uint32_t n)
-{
-    uint32_t l = 0;
-    while ((1u << l) < n) ++l;
-    return l;
-}
 inline hipStream_t raw(fwa_stream *s) { return s ? s->s : nullptr; }
 
 // A buffer / event handle whose context has been destroyed may still be freed, never used (include/fft_wgpu_amd.h,
@@ -216,20 +196,8 @@ Pipeline take_pipeline(fwa_plan *p);
 int32_t build_pipeline(fwa_plan *p, int64_t group, int64_t n_streams);
 
 // ---- plan.cpp ----
-int64_t choose_path(uint32_t n, uint64_t batch, uint32_t lf[3], bool *colsw = nullptr);
 int32_t setup_path(fwa_plan *p);
 size_t ctl_bytes(const fwa_plan *p);
-uint32_t tiled_swizzle_default(const fwa_plan *p);
-
-// ---- accessors comm.cpp was written against ----
-inline int32_t use_device(fwa_ctx *ctx)
-{
-    USE_DEVICE(ctx);
-    return FWA_OK;
-}
-inline int ctx_device(const fwa_ctx *ctx) { return ctx->device; }
-inline fwa_ctx *buf_ctx(const fwa_buf *b) { return b->ctx; }
-inline hipStream_t stream_raw(fwa_stream *s) { return s ? s->s : nullptr; }
-inline fwa_ctx *stream_ctx(fwa_stream *s) { return s ? s->ctx : nullptr; }
+uint32_t swizzle_default(const fwa_plan *p);  // the block -> tile map of a pipelined plan while "xcd_swizzle" is unset
 
 }  // namespace fwa_int

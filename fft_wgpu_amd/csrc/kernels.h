@@ -1,6 +1,7 @@
 // kernels.h -- launch wrappers implemented in kernels_*.hip (internal to the library).
 #pragma once
 #include "cplx.h"
+#include "schedule.h"  // the kernel limits (rows32_supported, colsw_width, ...): one definition for launchers and host
 
 namespace fwa {
 
@@ -40,8 +41,6 @@ hipError_t launch_small32(int dir, const v2f *src, v2f *dst, const v2f *tw, uint
                           hipStream_t st);
 // last pass of a two-pass plan n = n1 * 2^lg_l (lg_l = 9 .. 12, n <= 2^28): 16 adjacent rows per workgroup (8 from 2048-point rows), 32 points
 // per thread, transposed store out[k1 + n1*k2] (kernels_rows32.hip: k_rows32); tw = half table of W_{2^lg_l}
-bool rows32_supported(uint32_t lg_l);
-bool rows32_ring_supported(uint32_t lg_l, uint32_t in_cw);
 hipError_t setup_rows32_kernels();
 // in_cw = 0: `in` is the n1 x 2^lg_l matrix; in_cw = 32 / 64: the tile-contiguous ring written by k_colsw
 hipError_t launch_rows32(int dir, uint32_t lg_l, const v2f *in, v2f *out, const v2f *tw, uint32_t n1, uint64_t in_sb,
@@ -50,15 +49,12 @@ hipError_t launch_rows32(int dir, uint32_t lg_l, const v2f *in, v2f *out, const 
 // pass A with short columns and wide tiles (lg_l = 9: 512 rows x 32 columns, lg_l = 8: 256 x 64; 512 threads, two
 // workgroups per CU; kernels_cols32.hip: k_colsw), written through to the ring slab; tile_ring: tile-contiguous output
 // [tile][k1][width], else the matrix layout
-bool colsw_supported(uint32_t lg_l);
-uint32_t colsw_width(uint32_t lg_l);
 hipError_t setup_colsw_kernels();
 hipError_t launch_colsw(int dir, uint32_t lg_l, bool tile_ring, const v2f *in, v2f *out, const v2f *tw, const v2f *tw_lo,
                         const v2f *tw_hi, uint32_t pitch, uint64_t in_sb, uint64_t out_sb, uint32_t n_transforms,
                         uint32_t xcd_swizzle, hipStream_t st);
 // pass A with a 2048-point first factor (lg_l = 11, n = 2048 * pitch <= 2^28): 16 adjacent columns per workgroup, matrix
 // layout out (to the ring slab), four-step twiddle of domain n (kernels_cols32.hip: k_cols32); tw = half table of W_{2^lg_l}
-bool cols32_supported(uint32_t lg_l);
 hipError_t setup_cols32_kernels();
 hipError_t launch_cols32(int dir, uint32_t lg_l, const v2f *in, v2f *out, const v2f *tw, const v2f *tw_lo, const v2f *tw_hi,
                          uint32_t pitch, uint64_t in_sb, uint64_t out_sb, uint32_t n_transforms, uint32_t xcd_swizzle,

@@ -143,10 +143,6 @@ __global__ __launch_bounds__(512, 4) void k_colsw(const v2f *__restrict__ in, v2
     FWA_STAMP(3);
 }
 
-bool colsw_supported(uint32_t lg_l) { return lg_l == 8 || lg_l == 9; }
-uint32_t colsw_width(uint32_t lg_l) { return 1u << (14 - lg_l); }
-bool cols32_supported(uint32_t lg_l) { return lg_l == 11; }
-
 // Pickers: the output of both column kernels goes through to the ring slab the next pass reads (sc1).
 static KernelLaunch colsw_launch(int dir, uint32_t lg_l)
 {

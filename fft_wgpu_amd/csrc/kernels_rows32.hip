@@ -4,10 +4,6 @@
 
 namespace fwa {
 
-bool rows32_supported(uint32_t lg_l) { return lg_l >= 9 && lg_l <= 12; }
-// tile-contiguous ring input of width in_cw (written by k_colsw): rows of >= 32*in_cw points
-bool rows32_ring_supported(uint32_t lg_l, uint32_t in_cw) { return (in_cw == 32 || in_cw == 64) && lg_l >= 10 && lg_l <= 12 && (1u << (lg_l - 5)) >= in_cw; }
-
 // kernel = nullptr: no such row length, or no ring input of that width at this row length
 static KernelLaunch rows32_launch(int dir, uint32_t lg_l, uint32_t in_cw)
 {

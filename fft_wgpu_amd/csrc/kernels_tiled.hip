@@ -7,7 +7,7 @@ namespace fwa {
 // kernel = nullptr: no such length
 static KernelLaunch tile_launch(int dir, int mode, uint32_t lg_l, bool buf, int role)
 {
-    if (lg_l < 6 || lg_l > 10) return {};
+    if (!tile_supported(lg_l)) return {};
     return {dir == FWD ? tile_kernel<FWD>(mode, lg_l, buf, role) : tile_kernel<INV>(mode, lg_l, buf, role),
             (1u << lg_l) / 16 * TILE_CW, (int)tile_lds(lg_l, TILE_CW)};
 }

@@ -5,10 +5,6 @@
 // tables and scratch, exec only enqueues kernels on the caller's stream and allocates nothing.
 #include <algorithm>
 #include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <new>
 
 #include "internal.h"
@@ -17,56 +13,8 @@ using namespace fwa_int;
 
 namespace fwa_int {
 
-// Path and per-pass FFT lengths (log2) for a transform length; shared by fwa_plan_create and fwa_describe_path.
-// `batch` separates two regimes (profiles/round2/sweep_small_batch_latency.jsonl):
-//  * throughput (n * batch > 2^20 samples): few passes of fat tiles -- a 1024-point first pass (k_p1_gen / the 2^20
-//    pipeline, 64 KiB tiles of 512 threads) and 32-point-per-thread rows;
-//  * latency (at most 2^20 samples in flight, or a single 2^21 / 2^22 transform, or fewer than FEW_1M transforms of
-//    2^20): fat tiles leave most of the 256 CUs idle (one 2^16 transform = FOUR 1024 x 16 tiles), so the plan uses the
-//    smallest tiles instead -- balanced two passes up to 2^17, balanced three passes of 64/128-point tiles above
-//    (2^16 x 1: 11.9 us against 16.2; 2^18 x 1: 12.7 against 18.4; 2^20 x 1: 19 against 24).
-constexpr uint64_t FEW_1M = 4;
-int64_t choose_path(uint32_t n, uint64_t batch, uint32_t lf[3], bool *colsw)
-{
-    lf[0] = lf[1] = lf[2] = 0;
-    if (colsw) *colsw = false;
-    const uint32_t lg = ilog2(n);
-    if (n == 1) return PATH_IDENTITY;
-    if (n <= 32768) { lf[0] = lg; return PATH_SMALL; }
-    const bool few = (lg < 20 && batch <= ((1ull << 20) >> lg)) || (lg == 20 && batch < FEW_1M)
-        || ((lg == 21 || lg == 22) && batch == 1);
-    if (n == (1u << 20) && !few) { lf[0] = lf[1] = 10; return PATH_TWOPASS_1M; }
-    if (n <= (1u << 30)) {
-        // factors of 64..1024 each, 2048 for the rows of a two-pass plan (re-tunable: key "factors").  Throughput
-        // regime: two passes up to 2^19 and at 2^21 .. 2^23 (2048 / 4096-point passes), three otherwise; a 1024-point
-        // first pass (k_p1_gen) wherever the other factors stay >= 64, measured faster than a balanced split except
-        // at 2^22 (level) (profiles/round2/p1gen_sweep.jsonl, factor_sweep.jsonl, sweep_rows32.jsonl). Round 3
-        // (profiles/round3/sweep_colsw_32GiB.jsonl, sweep_factors_24_28_colsw.jsonl): short columns in wide tiles
-        // (k_colsw: 256 x 64 / 512 x 32, 512- / 256-byte row segments) beat the 1024 x 16 tile of k_p1_gen as pass A
-        // wherever the last pass keeps <= 1024-point rows: 2^16 .. 2^19 + 7-9 %, three-pass sizes 2^24 .. 2^28 + 2-16 %
-        // 1024 x 4096: k_p1_gen + k_rows32 (8 rows of 4096 per workgroup)
-        if (!few && lg == 22) { lf[0] = 10; lf[1] = 12; }
-        else if (!few && lg == 23) { lf[0] = 11; lf[1] = 12; }  // 2048 x 4096: k_cols32 + k_rows32
-        else if (few && lg <= 17) { lf[0] = lg / 2; lf[1] = lg - lf[0]; }
-        else if (!few && lg <= 18) { lf[0] = 8; lf[1] = lg - 8; if (colsw) *colsw = true; }   // 256 x (256 .. 1024)
-        else if (!few && lg == 19) { lf[0] = 9; lf[1] = 10; if (colsw) *colsw = true; }       // 512 x 1024
-        else if (!few && lg == 21) { lf[0] = 10; lf[1] = lg - 10; }
-        else if (!few && lg >= 24 && lg <= 28) {
-            lf[0] = 9; lf[1] = (lg - 9) / 2; lf[2] = lg - 9 - lf[1];
-            if (colsw) *colsw = true;
-        }
-        else if (!few && lg >= 29) { lf[0] = 10; lf[1] = (lg - 10) / 2; lf[2] = lg - 10 - lf[1]; }
-        // 16.4 us against 18.2 for 64 x 128 x 128 (sweep_factor_permutations_batch1.jsonl)
-        else if (few && lg == 20) { lf[0] = lf[1] = 6; lf[2] = 8; }
-        else for (uint32_t i = 0; i < 3; ++i) lf[i] = lg / 3 + (i >= 3 - lg % 3 ? 1 : 0);
-        return PATH_TILED;
-    }
-    return PATH_R2_GLOBAL;
-}
-
-// Kernel families, bit i set up by kFamilySetups[i]: each raises the dynamic-LDS limits of its kernels (kernels.h), once per
-// context, before the first plan that may launch one of them -- and only then: a plan of n <= 4096 loads no k_small32<14 / 15>.
-enum : uint32_t { FAM_SMALL32 = 1, FAM_1M = 2, FAM_ROWS32 = 4, FAM_COLSW = 8, FAM_COLS32 = 16, FAM_TILE = 32, FAM_LAB_RING = 64 };
+// Kernel families (FAM_* of schedule.h), bit i set up by kFamilySetups[i], once per context, before the first plan that may
+// launch one of them -- and only then: a plan of n <= 4096 loads no k_small32<14 / 15>.
 static hipError_t (*const kFamilySetups[])() = {
     fwa::setup_small32_kernels, fwa::setup_1m_kernels, fwa::setup_rows32_kernels, fwa::setup_colsw_kernels,
     fwa::setup_cols32_kernels, fwa::setup_tile_kernels,
@@ -75,25 +23,13 @@ static hipError_t (*const kFamilySetups[])() = {
 #endif
 };
 
-// The families a plan may launch on its path.  A tiled plan counts every pass-A and pass-C alternative that the keys "colsw",
-// "rows32", "p1_gen" and "tile_ring" can select without a new setup ("factors" and "path" run setup_path again).
+// The families a plan may launch on its path.  A tiled plan counts every kernel that the keys "colsw", "rows32", "p1_gen" and
+// "tile_ring" can select without a new setup ("factors" and "path" run setup_path again).
 static uint32_t path_families(const fwa_plan *p)
 {
-    switch (p->path) {
-        case PATH_SMALL: return p->n > 4096 ? FAM_SMALL32 : 0u;
-        case PATH_TWOPASS_1M: return FAM_1M;
-        case PATH_RING_1M: return FAM_LAB_RING;
-        case PATH_TILED: {
-            uint32_t f = 0;
-            if (fwa::colsw_supported(p->lf[0])) f |= FAM_COLSW;
-            if (fwa::cols32_supported(p->lf[0])) f |= FAM_COLS32;
-            if (p->lf[0] == 10) f |= FAM_1M;  // k_p1_gen
-            if (!p->lf[2] && fwa::rows32_supported(p->lf[1])) f |= FAM_ROWS32;
-            if (std::min(p->lf[0], p->lf[1]) <= 10) f |= FAM_TILE;  // 2048 / 4096-point passes: k_cols32 / k_rows32 only
-            return f;
-        }
-        default: return 0u;
-    }
+    if (p->path == PATH_TILED) return families(p->lg, p->lf);
+    if (p->path == PATH_SMALL) return p->n > 4096 ? FAM_SMALL32 : 0u;
+    return p->path == PATH_TWOPASS_1M ? FAM_1M : p->path == PATH_RING_1M ? FAM_LAB_RING : 0u;
 }
 
 // Everything a plan needs for its path: kernel attributes (once per context), twiddle tables (shared through the
@@ -164,23 +100,17 @@ size_t ctl_bytes(const fwa_plan *p)
 #endif
 }
 
-static fwa_buf *result_buffer(fwa_plan *p)
-{
-    // processor.rs:153-157, :335-339, :664-668
-    return (p->lg % 2 == 0) ? p->src : p->second;
-}
+// processor.rs:153-157, :335-339, :664-668
+static fwa_buf *result_buffer(fwa_plan *p) { return (p->lg % 2 == 0) ? p->src : p->second; }
 
-// Block -> tile map of the tiled plans' kernels (xcd_map, device_common.h) when the caller has not set "xcd_swizzle":
-// measured per size at the 32-GiB footprint, three interleaved runs (profiles/round4/sweep_tiled_block_maps.jsonl):
-// the k_colsw plans gain 2-4 % from XCD-contiguous runs (2^17 .. 2^19: bit 0; 2^16 and 1024 x 2048: with the CU
-// pairs, bits 0 + 2); 2^22 and up lose 1-10 %.
-uint32_t tiled_swizzle_default(const fwa_plan *p)
+// Block -> tile map (xcd_map, device_common.h) of a pipelined plan whose caller has not set "xcd_swizzle".  2^20 pipeline:
+// XCD-contiguous tiles + adjacent tiles on the two residents of a CU (bit 2: + 4-8 % for launches that have the chip to
+// themselves, + 0.6 % with two chains in flight: tile_1m.h xcd_block, profiles/round4/sweep_pair_map_two_chains.jsonl);
+// tiled plans: per size, resolved with the passes (schedule.h).
+uint32_t swizzle_default(const fwa_plan *p)
 {
-    if (p->lf[2]) return 0u;
-    if (p->colsw && p->lg == 16) return 5u;
-    if (p->colsw && p->lg >= 17 && p->lg <= 19) return 1u;
-    if (p->lg == 21 && p->lf[0] == 10 && p->lf[1] == 11) return 5u;
-    return 0u;
+    if (p->path == PATH_TWOPASS_1M) return 5u;
+    return p->path == PATH_TILED ? resolve_tiled(p->lg, p->lf, p->flags).xcd_swizzle : 0u;
 }
 
 // Run `body(group index, stream, chain index)` for every group, alternating over the plan's internal streams,
@@ -222,111 +152,86 @@ static int32_t run_groups(fwa_plan *plan, hipStream_t st, Body body)
     return FWA_OK;
 }
 
-
 // ---- the tiled path (PATH_TILED): n = N1*N2[*N3]; index n = (n1*N2 + n2)*N3 + n3, k = k1 + N1*(k2 + N2*k3) ----
 //   pass A: FFT over n1 (columns, four-step twiddle W_n), user buffer -> ring slab
 //   pass B: FFT over n2 per k1 (columns, twiddle W_{N2*N3}), in place in the slab            [three factors only]
 //   pass C: FFT over the contiguous axis with the transposed store, slab -> result buffer
+// Which kernel runs each pass is resolve_tiled's answer (schedule.h); the code below only fills in launch arguments.
 // What the passes of one exec share: factor sizes, the block -> tile map and the slab layout pass A leaves for pass C.
 struct TiledShape {
     uint64_t N, N1, N2, N3;
     bool three;
-    uint32_t swizzle;   // xcd_map bits handed to every kernel
-    // k_colsw writes the slab tile-contiguously ([tile][k1][ring_cw]) when the last pass (k_rows32) can read that layout
-    // back; 0 = matrix layout
-    uint32_t ring_cw;
+    uint32_t swizzle, ring_cw;   // xcd_map bits handed to every kernel; TiledSchedule::ring_cw
 };
 
-// One pass of a tiled exec: which kernel, and every launch argument except the group's pointers and transform count.
+// One pass of a tiled exec: the resolved kernel, and every launch argument except the group's pointers and transform count.
 // Built once per fwa_plan_exec by pass_a / pass_b / pass_c, immutable afterwards, called once per group.
 struct TiledPass {
-    enum Kernel { NONE, COLSW, COLS32, P1_GEN, TILE_COLS_K, ROWS32, TILE_ROWS_K } kernel = NONE;
+    TiledKernel kernel = TiledKernel::NONE;
     int dir = fwa::FWD;
     uint32_t lg_l = 0;                 // log2 of this pass's FFT length
     const v2f *tw = nullptr, *tw_lo = nullptr, *tw_hi = nullptr;
-    uint32_t pitch = 0;                // columns of the n1 x pitch matrix (COLSW, COLS32, P1_GEN)
-    uint32_t n1 = 0;                   // ROWS32: rows of the matrix
+    const v2f *tw_inner = nullptr;     // k_p1_gen: its first-stage table in place of tw
+    uint32_t pitch = 0;                // column kernels: columns of the n1 x pitch matrix
+    uint32_t n1 = 0;                   // k_rows32: rows of the matrix
     uint64_t sb = 0;                   // elements between transforms, in and out
     float scale = 1.0f;
     uint32_t swizzle = 0, ring_cw = 0;
-    fwa::TileArgs ta{};                // TILE_COLS_K / TILE_ROWS_K: complete except in / out
+    fwa::TileArgs ta{};                // k_tile: complete except in / out
     hipError_t operator()(const v2f *in, v2f *out, uint64_t cnt, hipStream_t s) const
     {
         switch (kernel) {
-            case COLSW:
+            case TiledKernel::COLSW:
                 return fwa::launch_colsw(dir, lg_l, ring_cw != 0, in, out, tw, tw_lo, tw_hi, pitch, sb, sb, (uint32_t)cnt,
                                          swizzle, s);
-            case COLS32:
+            case TiledKernel::COLS32:
                 return fwa::launch_cols32(dir, lg_l, in, out, tw, tw_lo, tw_hi, pitch, sb, sb, (uint32_t)cnt, swizzle, s);
-            case P1_GEN:
-                return fwa::launch_p1_gen(dir, true, in, out, tw, tw_lo, tw_hi, pitch, sb, sb, (uint32_t)cnt, swizzle, s);
-            case ROWS32:
+            case TiledKernel::P1_GEN:
+                return fwa::launch_p1_gen(dir, true, in, out, tw_inner, tw_lo, tw_hi, pitch, sb, sb, (uint32_t)cnt, swizzle, s);
+            case TiledKernel::ROWS32:
                 return fwa::launch_rows32(dir, lg_l, in, out, tw, n1, sb, sb, (uint32_t)cnt, scale, swizzle, ring_cw, s);
-            case TILE_COLS_K:
-            case TILE_ROWS_K: {
+            case TiledKernel::TILE_COLS:
+            case TiledKernel::TILE_ROWS: {
                 fwa::TileArgs t = ta;
                 t.in = in; t.out = out;
-                return fwa::launch_tile(dir, kernel == TILE_COLS_K ? fwa::TILE_COLS : fwa::TILE_ROWS_T, lg_l, t, cnt, s);
+                return fwa::launch_tile(dir, kernel == TiledKernel::TILE_COLS ? fwa::TILE_COLS : fwa::TILE_ROWS_T, lg_l, t, cnt, s);
             }
-            case NONE: break;
+            case TiledKernel::NONE: break;
         }
         return hipSuccess;
     }
 };
 
-static bool tiled_uses_colsw(const fwa_plan *p)
+static TiledShape tiled_shape(const fwa_plan *p, const TiledSchedule &sc)
 {
-    return p->colsw && fwa::colsw_supported(p->lf[0]) && p->lg <= 28;
-}
-
-static TiledShape tiled_shape(const fwa_plan *p)
-{
-    TiledShape sh{};
-    sh.three = p->lf[2] != 0;
-    sh.N = p->n;
-    sh.N1 = 1ull << p->lf[0]; sh.N2 = 1ull << p->lf[1]; sh.N3 = sh.three ? (1ull << p->lf[2]) : 1;
-    sh.swizzle = p->xcd_swizzle < 0 ? tiled_swizzle_default(p) : (uint32_t)p->xcd_swizzle;
-    const bool ring = tiled_uses_colsw(p) && p->tile_ring && !sh.three
-        && fwa::rows32_ring_supported(p->lf[1], fwa::colsw_width(p->lf[0]));
-    sh.ring_cw = ring ? fwa::colsw_width(p->lf[0]) : 0u;
-    return sh;
+    const bool three = sc.passes == 3;
+    return {p->n, 1ull << p->lf[0], 1ull << p->lf[1], three ? (1ull << p->lf[2]) : 1, three,
+            p->xcd_swizzle < 0 ? sc.xcd_swizzle : (uint32_t)p->xcd_swizzle, sc.ring_cw};
 }
 
 // pass A: columns of length N1 at pitch N / N1, user buffer -> slab
-static TiledPass pass_a(const fwa_plan *p, const TiledShape &sh, const Tables &tb, int dir)
+static TiledPass pass_a(TiledKernel kernel, const fwa_plan *p, const TiledShape &sh, const Tables &tb, int dir)
 {
     TiledPass ps;
+    ps.kernel = kernel;
     ps.dir = dir; ps.lg_l = p->lf[0]; ps.sb = sh.N; ps.swizzle = sh.swizzle; ps.ring_cw = sh.ring_cw;
     ps.pitch = (uint32_t)(sh.N / sh.N1);
-    ps.tw = tb.tw_l[0]; ps.tw_lo = tb.tw_lo1; ps.tw_hi = tb.tw_hi1;
-    ps.kernel = tiled_uses_colsw(p)                             ? TiledPass::COLSW     // 256 x 64 / 512 x 32 column tiles
-                : p->lf[0] > 10                                  ? TiledPass::COLS32    // 2048-point columns
-                : (p->lf[0] == 10 && p->p1_gen && tb.tw_inner)   ? TiledPass::P1_GEN    // the 2^20 column kernel at run-time pitch
-                                                                 : TiledPass::TILE_COLS_K;
-    switch (ps.kernel) {
-        case TiledPass::P1_GEN:
-            ps.tw = tb.tw_inner;
-            break;
-        case TiledPass::TILE_COLS_K: {
-            const uint32_t cw = fwa::TILE_CW;
-            fwa::TileArgs &t = ps.ta;
-            t.tw = tb.tw_l[0]; t.tw_lo = tb.tw_lo1; t.tw_hi = tb.tw_hi1;
-            t.scale = 1.0f; t.cw = cw; t.role = fwa::ROLE_FIRST; t.xcd_swizzle = sh.swizzle;
-            t.in_sb = t.out_sb = sh.N; t.in_s1 = t.out_s1 = 0; t.in_st = t.out_st = cw;
-            t.pitch = sh.N / sh.N1; t.out_stride = 0; t.d1_count = 1; t.tile_count = (uint32_t)(sh.N / sh.N1 / cw);
-            break;
-        }
-        default: break;
-    }
+    ps.tw = tb.tw_l[0]; ps.tw_lo = tb.tw_lo1; ps.tw_hi = tb.tw_hi1; ps.tw_inner = tb.tw_inner;
+    const uint32_t cw = fwa::TILE_CW;
+    fwa::TileArgs &t = ps.ta;
+    t.tw = tb.tw_l[0]; t.tw_lo = tb.tw_lo1; t.tw_hi = tb.tw_hi1;
+    t.scale = 1.0f; t.cw = cw; t.role = fwa::ROLE_FIRST; t.xcd_swizzle = sh.swizzle;
+    t.in_sb = t.out_sb = sh.N; t.in_s1 = t.out_s1 = 0; t.in_st = t.out_st = cw;
+    t.pitch = sh.N / sh.N1; t.out_stride = 0; t.d1_count = 1; t.tile_count = (uint32_t)(sh.N / sh.N1 / cw);
     return ps;
 }
 
 // pass B (three factors): columns of length N2 at pitch N3 inside every k1-plane, in place in the slab
-static TiledPass pass_b(const fwa_plan *p, const TiledShape &sh, const Tables &tb, int dir)
+static TiledPass pass_b(TiledKernel kernel, const fwa_plan *p, const TiledShape &sh, const Tables &tb, int dir)
 {
     TiledPass ps;
     if (!sh.three) return ps;   // kernel == NONE
-    ps.kernel = TiledPass::TILE_COLS_K;
+    ps.kernel = kernel;
     ps.dir = dir; ps.lg_l = p->lf[1];
     const uint32_t cw = fwa::TILE_CW;
     fwa::TileArgs &t = ps.ta;
@@ -338,33 +243,24 @@ static TiledPass pass_b(const fwa_plan *p, const TiledShape &sh, const Tables &t
 }
 
 // pass C: rows of the last axis, adjacent k1 per tile, transposed store into the result buffer (+ the 1/n of Inverse)
-static TiledPass pass_c(const fwa_plan *p, const TiledShape &sh, const Tables &tb, int dir, float scale)
+static TiledPass pass_c(TiledKernel kernel, const fwa_plan *p, const TiledShape &sh, const Tables &tb, int dir, float scale)
 {
     TiledPass ps;
     const uint32_t li = sh.three ? 2 : 1;
+    ps.kernel = kernel;
     ps.dir = dir; ps.lg_l = p->lf[li]; ps.sb = sh.N; ps.scale = scale; ps.swizzle = sh.swizzle; ps.ring_cw = sh.ring_cw;
     ps.tw = tb.tw_l[li]; ps.n1 = (uint32_t)sh.N1;
-    const bool rows32 = !sh.three && p->lg <= 28 && fwa::rows32_supported(p->lf[1])
-        && (p->rows32 || p->lf[1] > 10 || sh.ring_cw);   // 2048 / 4096-point rows and the tile ring exist only there
-    ps.kernel = rows32 ? TiledPass::ROWS32 : TiledPass::TILE_ROWS_K;
-    switch (ps.kernel) {
-        case TiledPass::TILE_ROWS_K: {
-            const uint32_t cw = fwa::TILE_CW;
-            fwa::TileArgs &t = ps.ta;
-            t.tw = tb.tw_l[li]; t.tw_lo = nullptr; t.tw_hi = nullptr;
-            t.scale = scale; t.cw = cw; t.role = fwa::ROLE_LAST; t.xcd_swizzle = sh.swizzle;
-            t.in_sb = t.out_sb = sh.N;
-            t.pitch = sh.N / sh.N1;  // distance between the rows k1 and k1 + 1
-            t.in_st = cw * (sh.N / sh.N1); t.out_st = cw; t.tile_count = (uint32_t)(sh.N1 / cw);
-            if (sh.three) { t.d1_count = (uint32_t)sh.N2; t.in_s1 = sh.N3; t.out_s1 = sh.N1; t.out_stride = sh.N1 * sh.N2; }
-            else { t.d1_count = 1; t.in_s1 = t.out_s1 = 0; t.out_stride = sh.N1; }
-            break;
-        }
-        default: break;
-    }
+    const uint32_t cw = fwa::TILE_CW;
+    fwa::TileArgs &t = ps.ta;
+    t.tw = tb.tw_l[li]; t.tw_lo = nullptr; t.tw_hi = nullptr;
+    t.scale = scale; t.cw = cw; t.role = fwa::ROLE_LAST; t.xcd_swizzle = sh.swizzle;
+    t.in_sb = t.out_sb = sh.N;
+    t.pitch = sh.N / sh.N1;  // distance between the rows k1 and k1 + 1
+    t.in_st = cw * (sh.N / sh.N1); t.out_st = cw; t.tile_count = (uint32_t)(sh.N1 / cw);
+    if (sh.three) { t.d1_count = (uint32_t)sh.N2; t.in_s1 = sh.N3; t.out_s1 = sh.N1; t.out_stride = sh.N1 * sh.N2; }
+    else { t.d1_count = 1; t.in_s1 = t.out_s1 = 0; t.out_stride = sh.N1; }
     return ps;
 }
-
 
 }  // namespace fwa_int
 
@@ -465,11 +361,9 @@ int32_t fwa_plan_create(fwa_ctx *ctx, int32_t kind, uint32_t fft_len, fwa_buf *s
         return done();
     }
 
-    {
-        bool cw = false;
-        p->path = choose_path(fft_len, p->batch, p->lf, &cw);
-        p->colsw = cw;
-    }
+    bool cw = false;
+    p->path = choose_path(fft_len, p->batch, p->lf, &cw);
+    p->flags.colsw = cw;
 
     // Forward/Inverse own their ping-pong partner (processor.rs:34-41,261-269).  It is only
     // materialised when the result must land there (odd log2 n) or the path ping-pongs.
@@ -556,10 +450,7 @@ int32_t fwa_plan_exec(fwa_plan *plan, fwa_stream *stream, fwa_buf **result)
         case PATH_TWOPASS_1M: {
             // in place at group granularity: 2^20 has even log2, the result buffer is src (processor.rs:153-157)
             const v2f *two = tb.tw_outer;
-            // default: XCD-contiguous tiles + adjacent tiles on the two residents of a CU (bit 2: + 4-8 % for
-            // launches that have the chip to themselves, + 0.6 % with two chains in flight: tile_1m.h xcd_block,
-            // profiles/round4/sweep_pair_map_two_chains.jsonl)
-            const uint32_t swz = plan->xcd_swizzle < 0 ? 5u : (uint32_t)plan->xcd_swizzle;
+            const uint32_t swz = plan->xcd_swizzle < 0 ? swizzle_default(plan) : (uint32_t)plan->xcd_swizzle;
             return run_groups(plan, st, [&](uint64_t g, uint64_t cnt, hipStream_t s, size_t c) {
                 // ring region of this chain: transform i -> slot i (ring_rotate > 1, laboratory: successive groups of a
                 // chain walk through ring_rotate such regions)
@@ -586,16 +477,19 @@ int32_t fwa_plan_exec(fwa_plan *plan, fwa_stream *stream, fwa_buf **result)
 #endif
         case PATH_TILED: {
             // Per group of transforms: pass A, user buffer -> ring slab; [pass B, in place in the slab]; pass C, slab ->
-            // result buffer (src for even log2 n -- in place at group granularity -- else second).  The three passes are
-            // built once per exec (TiledPass above: kernel choice + launch arguments, nothing on the heap) and only
-            // receive the group's pointers here.
-            const TiledShape shape = tiled_shape(plan);
-            const TiledPass pa = pass_a(plan, shape, tb, dir), pb = pass_b(plan, shape, tb, dir),
-                            pc = pass_c(plan, shape, tb, dir, scale);
+            // result buffer (src for even log2 n -- in place at group granularity -- else second).  The kernels are
+            // resolved and the three passes built once per exec (TiledPass above: launch arguments, nothing on the heap)
+            // and only receive the group's pointers here.
+            const TiledSchedule sc = resolve_tiled(plan->lg, plan->lf, plan->flags);
+            if (sc.a == TiledKernel::NONE || sc.c == TiledKernel::NONE || (sc.passes == 3 && sc.b == TiledKernel::NONE))
+                return fail(ctx, FWA_ERR_UNSUPPORTED, "no kernel for a pass of these factors");
+            const TiledShape shape = tiled_shape(plan, sc);
+            const TiledPass pa = pass_a(sc.a, plan, shape, tb, dir), pb = pass_b(sc.b, plan, shape, tb, dir),
+                            pc = pass_c(sc.c, plan, shape, tb, dir, scale);
             return run_groups(plan, st, [&](uint64_t g, uint64_t cnt, hipStream_t s, size_t c) {
                 v2f *slab = plan->ring + (uint64_t)c * G * N;
                 hipError_t le = pa(a + g * G * N, slab, cnt, s);
-                if (le == hipSuccess && pb.kernel != TiledPass::NONE) le = pb(slab, slab, cnt, s);
+                if (le == hipSuccess && pb.kernel != TiledKernel::NONE) le = pb(slab, slab, cnt, s);
                 if (le == hipSuccess) le = pc(slab, out + g * G * N, cnt, s);
                 return le;
             });

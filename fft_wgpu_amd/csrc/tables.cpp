@@ -3,13 +3,7 @@
 //
 // The reference builds one n/2-entry table per plan from f64 math rounded to f32 (src/processor.rs:43-49); every table
 // here follows that rule (tw_f64), factorised into two levels where a table of n entries would be too large.
-#include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <new>
 
 #include "internal.h"
 
@@ -52,40 +46,38 @@ int32_t upload_level(fwa_ctx *ctx, uint64_t cur, v2f **lo, v2f **hi)
     return s ? s : upload_table(ctx, h, hi);
 }
 
+// first-stage table of the 1024-point column kernels (k_p1_1m, k_p2_1m, k_p1_gen): [k1][n'] = W_1024^{n' k1}
+static int32_t upload_inner_table(fwa_ctx *ctx, v2f **d)
+{
+    std::vector<v2f> inner(1024);
+    for (uint32_t k1 = 0; k1 < 32; ++k1)
+        for (uint32_t q = 0; q < 32; ++q) inner[k1 * 32 + q] = tw_f64((uint64_t)k1 * q, 1024);
+    return upload_table(ctx, inner, d);
+}
+
 int32_t build_tables(fwa_ctx *ctx, uint32_t n, int64_t path, const uint32_t lf[3], Tables *t)
 {
     int32_t st = FWA_OK;
     if (path == PATH_SMALL) return n >= 2 ? upload_half_table(ctx, n, &t->tw_half) : FWA_OK;
     if (path == PATH_TWOPASS_1M) {
-        std::vector<v2f> inner(1024);
-        for (uint32_t k1 = 0; k1 < 32; ++k1)
-            for (uint32_t q = 0; q < 32; ++q) inner[k1 * 32 + q] = tw_f64((uint64_t)k1 * q, 1024);
-        st = upload_table(ctx, inner, &t->tw_inner);
+        if ((st = upload_inner_table(ctx, &t->tw_inner))) return st;
         const uint64_t N = 1ull << 20;
-        for (int wi = 0; wi < 1 && !st; ++wi) {   // one tile width ships: 16 columns
-            const uint32_t W = 16, tiles = 1024 / W;
-            std::vector<v2f> outer((size_t)tiles * 64 * W);
-            for (uint32_t tile = 0; tile < tiles; ++tile)
-                for (uint32_t k = 0; k < 32; ++k)
-                    for (uint32_t c = 0; c < W; ++c) {
-                        const uint64_t n2 = (uint64_t)W * tile + c;
-                        outer[(size_t)tile * 64 * W + k * W + c] = tw_f64(n2 * k, N);                // A[k1][c]
-                        outer[(size_t)tile * 64 * W + 32 * W + k * W + c] = tw_f64(32 * n2 * k, N);  // B[k2][c]
-                    }
-            st = upload_table(ctx, outer, &t->tw_outer);
-        }
-        return st;
+        const uint32_t W = 16, tiles = 1024 / W;   // one tile width ships: 16 columns
+        std::vector<v2f> outer((size_t)tiles * 64 * W);
+        for (uint32_t tile = 0; tile < tiles; ++tile)
+            for (uint32_t k = 0; k < 32; ++k)
+                for (uint32_t c = 0; c < W; ++c) {
+                    const uint64_t n2 = (uint64_t)W * tile + c;
+                    outer[(size_t)tile * 64 * W + k * W + c] = tw_f64(n2 * k, N);                // A[k1][c]
+                    outer[(size_t)tile * 64 * W + 32 * W + k * W + c] = tw_f64(32 * n2 * k, N);  // B[k2][c]
+                }
+        return upload_table(ctx, outer, &t->tw_outer);
     }
     if (path == PATH_TILED) {
         const uint32_t nf = lf[2] ? 3 : 2;
         for (uint32_t i = 0; i < nf && !st; ++i) st = upload_half_table(ctx, 1u << lf[i], &t->tw_l[i]);
         if (!st) st = upload_level(ctx, n, &t->tw_lo1, &t->tw_hi1);
-        if (!st && lf[0] == 10) {  // k_p1_gen's first-stage table [k1][n'] = W_1024^{n' k1}
-            std::vector<v2f> inner(1024);
-            for (uint32_t k1 = 0; k1 < 32; ++k1)
-                for (uint32_t q = 0; q < 32; ++q) inner[k1 * 32 + q] = tw_f64((uint64_t)k1 * q, 1024);
-            st = upload_table(ctx, inner, &t->tw_inner);
-        }
+        if (!st && needs_inner_table(lf)) st = upload_inner_table(ctx, &t->tw_inner);
         if (!st && nf == 3) st = upload_level(ctx, (uint64_t)n >> lf[0], &t->tw_lo_b, &t->tw_hi_b);
         return st;
     }

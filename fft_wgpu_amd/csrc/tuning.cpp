@@ -1,14 +1,6 @@
 // tuning.cpp -- fwa_plan_get_i64 / fwa_plan_set_i64: what a plan chose at creation, and the keys that re-tune it
 // before its first exec.  No key changes what a plan computes (tests/test_gpu_parity.py: every alternative is
 // bit-identical where it shares arithmetic); the reference has no counterpart (one radix-2 loop, src/kernel/fft4.wgsl).
-#include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <new>
-
 #include "internal.h"
 
 using namespace fwa_int;
@@ -26,11 +18,7 @@ int32_t fwa_plan_get_i64(const fwa_plan *plan, const char *key, int64_t *value)
     else if (k == "group") *value = plan->group;
     else if (k == "streams") *value = plan->n_streams;
     else if (k == "tile_w") *value = 16;   // one tile width ships (kept as a key: bench lines of every round carry it)
-    else if (k == "xcd_swizzle") {
-        const int64_t dflt = plan->path == PATH_TWOPASS_1M ? 5
-                             : (plan->path == PATH_TILED ? (int64_t)tiled_swizzle_default(plan) : 0);
-        *value = plan->xcd_swizzle < 0 ? dflt : plan->xcd_swizzle;
-    }
+    else if (k == "xcd_swizzle") *value = plan->xcd_swizzle < 0 ? (int64_t)swizzle_default(plan) : plan->xcd_swizzle;
     else if (k == "depth") *value = plan->depth;
     else if (k == "ring_slots") *value = plan->ring_slots;
     else if (k == "wgs") *value = plan->wgs;
@@ -45,10 +33,10 @@ int32_t fwa_plan_get_i64(const fwa_plan *plan, const char *key, int64_t *value)
         }
     }
     else if (k == "small_reg") *value = plan->small_reg;
-    else if (k == "p1_gen") *value = plan->p1_gen;
-    else if (k == "rows32") *value = plan->rows32;
-    else if (k == "colsw") *value = plan->colsw;
-    else if (k == "tile_ring") *value = plan->tile_ring;
+    else if (k == "p1_gen") *value = plan->flags.p1_gen;
+    else if (k == "rows32") *value = plan->flags.rows32;
+    else if (k == "colsw") *value = plan->flags.colsw;
+    else if (k == "tile_ring") *value = plan->flags.tile_ring;
     else if (k == "ring_rotate") *value = plan->ring_rotate;
     else if (k == "factors") *value = plan->lf[0] | (plan->lf[1] << 8) | (plan->lf[2] << 16);
     // other holders: cache + plans
@@ -60,7 +48,7 @@ int32_t fwa_plan_get_i64(const fwa_plan *plan, const char *key, int64_t *value)
         switch (plan->path) {
             case PATH_TWOPASS_1M: *value = 2 * ng; break;
             case PATH_RING_1M: *value = 1; break;
-            case PATH_TILED: *value = (plan->lf[2] ? 3 : 2) * ng; break;
+            case PATH_TILED: *value = resolve_tiled(plan->lg, plan->lf, plan->flags).passes * ng; break;
             case PATH_R2_GLOBAL: *value = plan->lg; break;
             case PATH_IDENTITY: *value = (plan->kind == FWA_INVERSE_SCALED) ? 1 : 0; break;
             default: *value = 1;
@@ -132,21 +120,13 @@ int32_t fwa_plan_set_i64(fwa_plan *plan, const char *key, int64_t value)
     }
     if (k == "factors") {
         // re-factorise a multi-pass plan: value = log2(N1) | log2(N2) << 8 | log2(N3) << 16 (N3 = 0: two passes), every
-        // factor 64..1024, product n.  A tuning knob: every factorisation computes the same transform.
+        // factor a length its pass has a kernel for, product n.  A tuning knob: every factorisation computes the same transform.
         if (plan->path != PATH_TILED && plan->path != PATH_TWOPASS_1M)
             return fail(ctx, FWA_ERR_UNSUPPORTED, "key only applies to multi-pass plans");
         const uint32_t f[3] = {(uint32_t)value & 255u, (uint32_t)(value >> 8) & 255u, (uint32_t)(value >> 16) & 255u};
-        const uint32_t nf = f[2] ? 3 : 2;
-        uint32_t sum = 0;
-        for (uint32_t i = 0; i < nf; ++i) {
-            // 2048: as the first factor (k_cols32); 2048 / 4096: as the second of two (k_rows32); n <= 2^28
-            const uint32_t top = plan->lg > 28 ? 10u : (i == 0 ? 11u : ((nf == 2 && i == 1) ? 12u : 10u));
-            if (f[i] < 6 || f[i] > top)
-                return fail(ctx, FWA_ERR_INVALID_ARG,
-                            "every factor must be 2^6..2^10 (2^11: first; 2^11, 2^12: second of two)");
-            sum += f[i];
-        }
-        if (sum != plan->lg || (value >> 24))
+        if (!factors_valid(plan->lg, f))
+            return fail(ctx, FWA_ERR_INVALID_ARG, "every factor must be 2^6..2^10 (2^11: first; 2^11, 2^12: second of two)");
+        if (f[0] + f[1] + f[2] != plan->lg || (value >> 24))
             return fail(ctx, FWA_ERR_INVALID_ARG, "factors do not multiply to fft_len");
         const int64_t old_path = plan->path;
         uint32_t old_lf[3] = {plan->lf[0], plan->lf[1], plan->lf[2]};
@@ -158,8 +138,8 @@ int32_t fwa_plan_set_i64(fwa_plan *plan, const char *key, int64_t value)
     }
     if (k == "p1_gen" || k == "rows32" || k == "colsw" || k == "tile_ring") {
         if (plan->path != PATH_TILED) return fail(ctx, FWA_ERR_UNSUPPORTED, "key only applies to tiled plans");
-        int64_t &flag = k == "p1_gen" ? plan->p1_gen : k == "rows32" ? plan->rows32
-                        : k == "colsw" ? plan->colsw : plan->tile_ring;
+        TiledFlags &fl = plan->flags;
+        int64_t &flag = k == "p1_gen" ? fl.p1_gen : k == "rows32" ? fl.rows32 : k == "colsw" ? fl.colsw : fl.tile_ring;
         flag = value != 0;
         return FWA_OK;
     }
