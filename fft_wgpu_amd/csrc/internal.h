@@ -3,10 +3,11 @@
 // The host side of the C ABI (include/fft_wgpu_amd.h) is split by concern:
 //   ctx_streams.cpp  contexts, error strings, device enumeration, the slab rule, streams (+ the overlap check), events
 //   buffers.cpp      device / pinned memory, uploads, downloads, copies (peer copies across contexts), synthetic data
-//   tables.cpp       twiddle tables (reference twiddle rule src/processor.rs:43-49), the ring pool, pipeline objects
+//   tables.cpp       twiddle tables (reference twiddle rule src/processor.rs:43-49), the ring pool, build_pipeline /
+//                    release_pipeline: the only code that allocates or frees what a Pipeline (below) holds
 //   schedule.h       path choice, kernel limits and the kernel of every pass of a tiled plan: pure integer logic, no HIP
 //   plan.cpp         plan create / destroy / exec (the four plan objects of src/processor.rs)
-//   tuning.cpp       fwa_plan_get_i64 / fwa_plan_set_i64
+//   tuning.cpp       fwa_plan_get_i64 / fwa_plan_set_i64; every key that rebuilds the pipeline goes through retune()
 //   comm.cpp         fwa_comm_*: slab movement over RCCL
 #pragma once
 #include <hip/hip_runtime.h>
@@ -51,6 +52,20 @@ struct Tables {
                        tw_hi_b})
             if (t) (void)hipFree(t);
     }
+};
+
+// What a pipelined plan (two-pass 2^20, tiled; laboratory: the persistent ring) runs on, and its geometry.  A plan has one;
+// build_pipeline makes a new one and swaps it in, release_pipeline is the only code that frees any part of it.
+struct Pipeline {
+    v2f *ring = nullptr;               // scratch: group * n_streams [* ring_rotate] transforms
+    uint64_t ring_bytes = 0;
+    uint32_t *ctl = nullptr;           // PATH_RING_1M: ticket, error word, per-transform hand-off counters
+    uint64_t ctl_bytes = 0;
+    std::vector<hipStream_t> streams;  // chains the groups alternate over: borrowed from ctx->chains, empty for one chain
+    std::vector<hipEvent_t> done;      // join event of every chain
+    hipEvent_t fork = nullptr;
+    int64_t group = 16;                // transforms per launch
+    int64_t n_streams = 2;             // chains
 };
 
 }  // namespace fwa_int
@@ -115,11 +130,7 @@ struct fwa_plan {
     std::shared_ptr<fwa_int::Tables> tb;    // shared through ctx->tables
     v2f *tw_half_private = nullptr;  // forced literal path on a size whose cached tables have no n/2 table
     uint32_t lf[3] = {0, 0, 0};    // tiled path: log2 of the factors (lf[2] = 0 for two factors)
-    // pipeline state (two-pass 2^20 and tiled paths): groups of transforms alternate over internal streams
-    v2f *ring = nullptr;
-    uint64_t ring_bytes = 0;
-    int64_t group = 16;            // transforms per launch
-    int64_t n_streams = 2;         // internal streams (chains) the groups alternate over
+    fwa_int::Pipeline pipe;        // two-pass 2^20 and tiled paths: groups of transforms alternate over internal streams
     // XCD-aware block -> tile mapping (xcd_map bits): -1 = per-path, per-size default (swizzle_default, plan.cpp)
     int64_t xcd_swizzle = -1;
     fwa_int::TiledFlags flags;     // tiled plans: the keys "colsw", "rows32", "p1_gen", "tile_ring" (schedule.h)
@@ -128,15 +139,11 @@ struct fwa_plan {
     int64_t ring_rotate = 1;
     // n <= 32768: 1 = k_chunk / k_small32; laboratory: 3 = direct 16-point kernels (16 .. 4096), 2 = + wave shuffles
     int64_t small_reg = 1;
-    std::vector<hipStream_t> istreams;
-    std::vector<hipEvent_t> idone;
-    hipEvent_t ev_fork = nullptr;
     // the caller's stream of the last exec that used the ring: fwa_plan_destroy waits for the work enqueued there (an
     // event per exec would cost 4-5 us on the 1-3-launch latency shapes)
     hipStream_t last_stream = nullptr;
     bool ran_on_stream = false;
     // persistent 2^20 pipeline (PATH_RING_1M)
-    uint32_t *ring_ctl = nullptr;  // ticket, error word, per-transform hand-off counters
     int64_t depth = 8;             // pass-2 tiles of transform t run beside pass-1 tiles of transform t + depth
     int64_t ring_slots = 12;       // transforms of intermediate kept (>= depth + 1)
     int64_t wgs = 512;             // persistent workgroups (2 per CU)
@@ -181,23 +188,13 @@ int32_t overlapping_stream(fwa_ctx *ctx, const std::vector<hipStream_t> &peers, 
 int32_t chain_streams(fwa_ctx *ctx, size_t n);  // the context's chain streams, created (and checked) on demand
 
 // ---- tables.cpp ----
-struct Pipeline {
-    v2f *ring = nullptr;
-    uint64_t ring_bytes = 0;
-    std::vector<hipStream_t> streams;
-    std::vector<hipEvent_t> done;
-    hipEvent_t fork = nullptr;
-};
 int32_t upload_half_table(fwa_ctx *ctx, uint32_t n, v2f **d);
 int32_t build_tables(fwa_ctx *ctx, uint32_t n, int64_t path, const uint32_t lf[3], Tables *t);
-void *pool_take(fwa_ctx *ctx, uint64_t bytes);
-void destroy_pipeline_objects(fwa_ctx *ctx, Pipeline &pl, bool pool_ring);
-Pipeline take_pipeline(fwa_plan *p);
+void release_pipeline(fwa_ctx *ctx, Pipeline &pl, bool pool_ring);
 int32_t build_pipeline(fwa_plan *p, int64_t group, int64_t n_streams);
 
 // ---- plan.cpp ----
 int32_t setup_path(fwa_plan *p);
-size_t ctl_bytes(const fwa_plan *p);
 uint32_t swizzle_default(const fwa_plan *p);  // the block -> tile map of a pipelined plan while "xcd_swizzle" is unset
 
 }  // namespace fwa_int

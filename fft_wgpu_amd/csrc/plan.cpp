@@ -90,16 +90,6 @@ int32_t setup_path(fwa_plan *p)
     return FWA_OK;
 }
 
-size_t ctl_bytes(const fwa_plan *p)
-{
-#ifdef FWA_LAB
-    return fwa::ring_ctl_bytes(p->batch);
-#else
-    (void)p;
-    return 0;
-#endif
-}
-
 // processor.rs:153-157, :335-339, :664-668
 static fwa_buf *result_buffer(fwa_plan *p) { return (p->lg % 2 == 0) ? p->src : p->second; }
 
@@ -119,13 +109,14 @@ template <class Body>
 static int32_t run_groups(fwa_plan *plan, hipStream_t st, Body body)
 {
     fwa_ctx *ctx = plan->ctx;
-    const uint64_t G = (uint64_t)plan->group, n_groups = (plan->batch + G - 1) / G;
-    const size_t ns = plan->istreams.size();
-    if (plan->batch && !plan->ring)
+    const Pipeline &pl = plan->pipe;
+    const uint64_t G = (uint64_t)pl.group, n_groups = (plan->batch + G - 1) / G;
+    const size_t ns = pl.streams.size();
+    if (plan->batch && !pl.ring)
         return fail(ctx, FWA_ERR_INVALID_ARG, "plan has no scratch ring (a failed re-tune?)");
     if (ns) {
-        HIP_TRY(ctx, hipEventRecord(plan->ev_fork, st));
-        for (size_t i = 0; i < ns; ++i) HIP_TRY(ctx, hipStreamWaitEvent(plan->istreams[i], plan->ev_fork, 0));
+        HIP_TRY(ctx, hipEventRecord(pl.fork, st));
+        for (size_t i = 0; i < ns; ++i) HIP_TRY(ctx, hipStreamWaitEvent(pl.streams[i], pl.fork, 0));
     }
     hipError_t e = hipSuccess;
     for (uint64_t g = 0; g < n_groups && e == hipSuccess; ++g) {
@@ -134,15 +125,15 @@ static int32_t run_groups(fwa_plan *plan, hipStream_t st, Body body)
 #ifdef FWA_LAB
         if (plan->inject_fail_group == (int64_t)g) { plan->inject_fail_group = -1; e = hipErrorLaunchFailure; break; }
 #endif
-        e = body(g, cnt, ns ? plan->istreams[c] : st, c);
+        e = body(g, cnt, ns ? pl.streams[c] : st, c);
     }
     // Join the chains back to the caller's stream ALSO when a launch failed: the groups enqueued before the failure
     // keep running on the chains, and whatever the caller enqueues next on `st` (a copy of the partial result, the
     // free of the buffer) must be ordered behind them.
     hipError_t je = hipSuccess;
     for (size_t i = 0; i < ns; ++i) {
-        hipError_t r = hipEventRecord(plan->idone[i], plan->istreams[i]);
-        if (r == hipSuccess) r = hipStreamWaitEvent(st, plan->idone[i], 0);
+        hipError_t r = hipEventRecord(pl.done[i], pl.streams[i]);
+        if (r == hipSuccess) r = hipStreamWaitEvent(st, pl.done[i], 0);
         if (r != hipSuccess && je == hipSuccess) je = r;
     }
     plan->last_stream = st;
@@ -276,7 +267,7 @@ int32_t fwa_plan_destroy(fwa_plan *plan)
     // for, through a marker on the stream that exec was enqueued on -- other streams and contexts keep running (a
     // device-wide synchronise here stalled them all and is illegal while any stream captures a graph).  An exec that
     // was captured into a graph enqueued nothing real: the plan must outlive the graphs that replay it.
-    if (plan->frozen && plan->ring) {
+    if (plan->frozen && plan->pipe.ring) {
         hipEvent_t ev = nullptr;
         bool waited = false;
         // only a stream that is known to be alive can take the marker: the null stream, or a stream of this context's
@@ -296,9 +287,7 @@ int32_t fwa_plan_destroy(fwa_plan *plan)
             (void)hipDeviceSynchronize();
         }
     }
-    Pipeline pl = take_pipeline(plan);
-    destroy_pipeline_objects(plan->ctx, pl, true);
-    if (plan->ring_ctl) (void)hipFree(plan->ring_ctl);
+    release_pipeline(plan->ctx, plan->pipe, true);
     if (plan->tw_half_private) (void)hipFree(plan->tw_half_private);
     if (plan->second_owned && plan->own_second.p) (void)hipFree(plan->own_second.p);
     delete plan;
@@ -417,7 +406,8 @@ int32_t fwa_plan_exec(fwa_plan *plan, fwa_stream *stream, fwa_buf **result)
     v2f *b = static_cast<v2f *>(plan->second->p);
     v2f *out = static_cast<v2f *>(res->p);
     const Tables &tb = *plan->tb;
-    const uint64_t N = plan->n, G = (uint64_t)plan->group;
+    const Pipeline &pl = plan->pipe;
+    const uint64_t N = plan->n, G = (uint64_t)pl.group;
 
     switch (plan->path) {
         case PATH_IDENTITY:
@@ -454,9 +444,9 @@ int32_t fwa_plan_exec(fwa_plan *plan, fwa_stream *stream, fwa_buf **result)
             return run_groups(plan, st, [&](uint64_t g, uint64_t cnt, hipStream_t s, size_t c) {
                 // ring region of this chain: transform i -> slot i (ring_rotate > 1, laboratory: successive groups of a
                 // chain walk through ring_rotate such regions)
-                const uint64_t round = g / (plan->istreams.empty() ? 1 : plan->istreams.size());
-                v2f *slab = plan->ring + (round % (uint64_t)plan->ring_rotate) *
-                                             (uint64_t)plan->n_streams * G * N + (uint64_t)c * G * N;
+                const uint64_t round = g / (pl.streams.empty() ? 1 : pl.streams.size());
+                v2f *slab = pl.ring + (round % (uint64_t)plan->ring_rotate) *
+                                          (uint64_t)pl.n_streams * G * N + (uint64_t)c * G * N;
                 hipError_t le = fwa::launch_p1_1m(dir, a + g * G * N, slab, tb.tw_inner, two, (uint32_t)cnt, swz, s);
                 if (le != hipSuccess) return le;
                 return fwa::launch_p2_1m(dir, slab, out + g * G * N, tb.tw_inner, (uint32_t)cnt, scale, swz, s);
@@ -464,11 +454,11 @@ int32_t fwa_plan_exec(fwa_plan *plan, fwa_stream *stream, fwa_buf **result)
         }
 #ifdef FWA_LAB
         case PATH_RING_1M: {
-            if (!plan->ring || !plan->ring_ctl)
+            if (!pl.ring || !pl.ctl)
                 return fail(ctx, FWA_ERR_INVALID_ARG, "plan has no scratch ring (a failed re-tune?)");
             const uint64_t slots = (uint64_t)plan->ring_slots < plan->batch ? (uint64_t)plan->ring_slots : plan->batch;
             const uint64_t depth = (uint64_t)plan->depth < slots ? (uint64_t)plan->depth : (slots > 1 ? slots - 1 : 1);
-            e = fwa::launch_ring_1m(dir, a, out, plan->ring, tb.tw_inner, tb.tw_outer, plan->ring_ctl,
+            e = fwa::launch_ring_1m(dir, a, out, pl.ring, tb.tw_inner, tb.tw_outer, pl.ctl,
                                     (uint32_t)plan->batch,
                                     (uint32_t)depth, (uint32_t)(slots > depth ? slots : depth + 1),
                                         (uint32_t)plan->wgs, scale, st);
@@ -487,7 +477,7 @@ int32_t fwa_plan_exec(fwa_plan *plan, fwa_stream *stream, fwa_buf **result)
             const TiledPass pa = pass_a(sc.a, plan, shape, tb, dir), pb = pass_b(sc.b, plan, shape, tb, dir),
                             pc = pass_c(sc.c, plan, shape, tb, dir, scale);
             return run_groups(plan, st, [&](uint64_t g, uint64_t cnt, hipStream_t s, size_t c) {
-                v2f *slab = plan->ring + (uint64_t)c * G * N;
+                v2f *slab = pl.ring + (uint64_t)c * G * N;
                 hipError_t le = pa(a + g * G * N, slab, cnt, s);
                 if (le == hipSuccess && pb.kernel != TiledKernel::NONE) le = pb(slab, slab, cnt, s);
                 if (le == hipSuccess) le = pc(slab, out + g * G * N, cnt, s);

@@ -1,9 +1,10 @@
-// tables.cpp -- twiddle tables (shared through the context's plan cache), the ring pool and the pipeline objects
-// (ring slab, chain streams, fork / join events) of the multi-pass plans.
+// tables.cpp -- twiddle tables (shared through the context's plan cache), the ring pool and the Pipeline of the multi-pass
+// plans (ring slab, chain streams, fork / join events, laboratory control words): built and released here only.
 //
 // The reference builds one n/2-entry table per plan from f64 math rounded to f32 (src/processor.rs:43-49); every table
 // here follows that rule (tw_f64), factorised into two levels where a table of n entries would be too large.
 #include <cmath>
+#include <utility>
 
 #include "internal.h"
 
@@ -84,21 +85,27 @@ int32_t build_tables(fwa_ctx *ctx, uint32_t n, int64_t path, const uint32_t lf[3
     return FWA_OK;
 }
 
-// newest pooled ring of exactly this size, or nullptr
-void *pool_take(fwa_ctx *ctx, uint64_t bytes)
+// The ring of pl.ring_bytes bytes: the newest pooled one of exactly that size, else a new allocation.
+static int32_t alloc_ring(fwa_ctx *ctx, Pipeline &pl)
 {
+    if (!pl.ring_bytes) return FWA_OK;
     for (size_t i = ctx->free_rings.size(); i-- > 0;)
-        if (ctx->free_rings[i].first == bytes) {
-            void *p = ctx->free_rings[i].second;
-            ctx->free_ring_bytes -= bytes;
+        if (ctx->free_rings[i].first == pl.ring_bytes) {
+            pl.ring = static_cast<v2f *>(ctx->free_rings[i].second);
+            ctx->free_ring_bytes -= pl.ring_bytes;
             ctx->free_rings.erase(ctx->free_rings.begin() + (std::ptrdiff_t)i);
             ++ctx->n_ring_reuses;
-            return p;
+            return FWA_OK;
         }
-    return nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&pl.ring), pl.ring_bytes);
+    if (e != hipSuccess) { pl.ring = nullptr; return fail_hip(ctx, e, "hipMalloc(ring)"); }
+    ++ctx->n_ring_allocs;
+    return FWA_OK;
 }
 
-void destroy_pipeline_objects(fwa_ctx *ctx, Pipeline &pl, bool pool_ring)
+// Everything a Pipeline holds goes here and nowhere else: events destroyed, the ring pooled (or freed), the control words
+// freed.  The geometry (group, n_streams) stays: "group" / "streams" keep answering on a plan that gave its ring up.
+void release_pipeline(fwa_ctx *ctx, Pipeline &pl, bool pool_ring)
 {
     // pl.streams are borrowed from the context (ctx->chains)
     for (auto e : pl.done) (void)hipEventDestroy(e);
@@ -119,92 +126,62 @@ void destroy_pipeline_objects(fwa_ctx *ctx, Pipeline &pl, bool pool_ring)
         } else {
             (void)hipFree(pl.ring);
         }
-        pl.ring = nullptr;
-        pl.ring_bytes = 0;
     }
+    if (pl.ctl) (void)hipFree(pl.ctl);
+    pl.ring = nullptr; pl.ctl = nullptr;
+    pl.ring_bytes = pl.ctl_bytes = 0;
 }
 
-Pipeline take_pipeline(fwa_plan *p)
-{
-    Pipeline pl;
-    pl.ring = p->ring; pl.ring_bytes = p->ring_bytes; pl.streams.swap(p->istreams); pl.done.swap(p->idone);
-    pl.fork = p->ev_fork;
-    p->ring = nullptr; p->ring_bytes = 0; p->ev_fork = nullptr;
-    return pl;
-}
-
-// Allocate the scratch ring and the internal streams of the pipelined paths.  The new objects are built first
-// and swapped in only on success, so a failed re-tune (e.g. a group too large for the free memory) leaves the
-// plan exactly as it was.
+// Allocate the scratch ring and the internal streams of the pipelined paths.  The new Pipeline is built completely first
+// and swapped in only on success (the new ring is taken before the old one is pooled: the ring counters show it), so a
+// failed re-tune (e.g. a group too large for the free memory) leaves the plan exactly as it was.
 int32_t build_pipeline(fwa_plan *p, int64_t group, int64_t n_streams)
 {
     fwa_ctx *ctx = p->ctx;
+    Pipeline pl;
+    auto finish = [&](int32_t st) {
+        if (!st) std::swap(p->pipe, pl);
+        release_pipeline(ctx, pl, st == FWA_OK);   // the old pipeline on success, else the unfinished new one
+        return st;
+    };
 #ifdef FWA_LAB
     if (p->path == PATH_RING_1M) {
         // one launch, no internal streams: ring of min(ring_slots, batch) transforms + the control words
-        Pipeline pl;
         const uint64_t slots = (uint64_t)p->ring_slots < p->batch ? (uint64_t)p->ring_slots : p->batch;
+        pl.group = p->pipe.group; pl.n_streams = p->pipe.n_streams;
         pl.ring_bytes = slots * (sizeof(v2f) << 20);
-        uint32_t *ctl = nullptr;
+        if (int32_t st = alloc_ring(ctx, pl)) return finish(st);
         if (pl.ring_bytes) {
-            if (void *pooled = pool_take(ctx, pl.ring_bytes)) {
-                pl.ring = static_cast<v2f *>(pooled);
-            } else {
-                hipError_t e = hipMalloc(reinterpret_cast<void **>(&pl.ring), pl.ring_bytes);
-                if (e != hipSuccess) return fail_hip(ctx, e, "hipMalloc(ring)");
-                ++ctx->n_ring_allocs;
-            }
-            hipError_t e = hipMalloc(reinterpret_cast<void **>(&ctl), fwa::ring_ctl_bytes(p->batch));
-            if (e != hipSuccess) { destroy_pipeline_objects(ctx, pl, false); return fail_hip(ctx, e,
-                "hipMalloc(ring control)"); }
+            pl.ctl_bytes = fwa::ring_ctl_bytes(p->batch);
+            hipError_t e = hipMalloc(reinterpret_cast<void **>(&pl.ctl), pl.ctl_bytes);
+            if (e != hipSuccess) { pl.ctl = nullptr; return finish(fail_hip(ctx, e, "hipMalloc(ring control)")); }
         }
-        Pipeline old = take_pipeline(p);
-        destroy_pipeline_objects(ctx, old, true);
-        if (p->ring_ctl) (void)hipFree(p->ring_ctl);
-        p->ring_ctl = ctl;
-        p->ring = pl.ring; p->ring_bytes = pl.ring_bytes;
-        return FWA_OK;
+        return finish(FWA_OK);
     }
 #endif
-    if (p->path != PATH_TWOPASS_1M && p->path != PATH_TILED) return FWA_OK;
+    if (!is_pipelined(p->path)) return FWA_OK;
     if (group < 1) group = 1;
     if ((uint64_t)group > p->batch && p->batch) group = (int64_t)p->batch;
     const uint64_t n_groups = p->batch ? (p->batch + group - 1) / group : 0;
     if (n_streams < 1) n_streams = 1;
     if ((uint64_t)n_streams > n_groups && n_groups) n_streams = (int64_t)n_groups;
-    Pipeline pl;
+    pl.group = group; pl.n_streams = n_streams;
     const uint64_t slots = (uint64_t)group * (uint64_t)n_streams * (uint64_t)p->ring_rotate;  // transforms in the ring
     pl.ring_bytes = p->batch ? slots * (uint64_t)p->n * sizeof(v2f) : 0;
-    auto bail = [&](int32_t st) { destroy_pipeline_objects(ctx, pl, false); return st; };
-    if (pl.ring_bytes) {
-        if (void *pooled = pool_take(ctx, pl.ring_bytes)) {
-            pl.ring = static_cast<v2f *>(pooled);
-        } else {
-            hipError_t e = hipMalloc(reinterpret_cast<void **>(&pl.ring), pl.ring_bytes);
-            if (e != hipSuccess) { pl.ring = nullptr; return bail(fail_hip(ctx, e, "hipMalloc(ring)")); }
-            ++ctx->n_ring_allocs;
-        }
-        if (n_streams > 1) {
-            int32_t cs = chain_streams(ctx, (size_t)n_streams);
-            if (cs) return bail(cs);
-            hipError_t e = hipEventCreateWithFlags(&pl.fork, hipEventDisableTiming);
-            if (e != hipSuccess) { pl.fork = nullptr; return bail(fail_hip(ctx, e, "hipEventCreate")); }
-            for (int64_t i = 0; i < n_streams; ++i) {
-                hipEvent_t ev;
-                pl.streams.push_back(ctx->chains[(size_t)i]);
-                e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-                if (e != hipSuccess) return bail(fail_hip(ctx, e, "hipEventCreate"));
-                pl.done.push_back(ev);
-            }
+    if (int32_t st = alloc_ring(ctx, pl)) return finish(st);
+    if (pl.ring_bytes && n_streams > 1) {
+        if (int32_t cs = chain_streams(ctx, (size_t)n_streams)) return finish(cs);
+        hipError_t e = hipEventCreateWithFlags(&pl.fork, hipEventDisableTiming);
+        if (e != hipSuccess) { pl.fork = nullptr; return finish(fail_hip(ctx, e, "hipEventCreate")); }
+        for (int64_t i = 0; i < n_streams; ++i) {
+            hipEvent_t ev;
+            pl.streams.push_back(ctx->chains[(size_t)i]);
+            e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+            if (e != hipSuccess) return finish(fail_hip(ctx, e, "hipEventCreate"));
+            pl.done.push_back(ev);
         }
     }
-    Pipeline old = take_pipeline(p);
-    destroy_pipeline_objects(ctx, old, true);
-    p->ring = pl.ring; p->ring_bytes = pl.ring_bytes; p->istreams.swap(pl.streams); p->idone.swap(pl.done);
-    p->ev_fork = pl.fork;
-    p->group = group;
-    p->n_streams = n_streams;
-    return FWA_OK;
+    return finish(FWA_OK);
 }
 
 }  // namespace fwa_int

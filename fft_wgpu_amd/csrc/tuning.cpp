@@ -5,18 +5,37 @@
 
 using namespace fwa_int;
 
+// One re-tune: `change` assigns to the choice a plan can re-tune -- path, factors and the laboratory's ring_rotate, depth
+// and ring_slots -- then the plan is set up again (setup_path: tables + pipeline with the default geometry) or only its
+// pipeline rebuilt with the geometry it has.  Both swap their result in only once it is complete, so putting the choice
+// back is all a failure needs: the plan is then exactly as it was.
+template <class Change>
+static int32_t retune(fwa_plan *p, bool new_path, Change change)
+{
+    const int64_t old[4] = {p->path, p->ring_rotate, p->depth, p->ring_slots};
+    const uint32_t old_lf[3] = {p->lf[0], p->lf[1], p->lf[2]};
+    change();
+    const int32_t st = new_path ? setup_path(p) : build_pipeline(p, p->pipe.group, p->pipe.n_streams);
+    if (st) {
+        p->path = old[0]; p->ring_rotate = old[1]; p->depth = old[2]; p->ring_slots = old[3];
+        for (int i = 0; i < 3; ++i) p->lf[i] = old_lf[i];
+    }
+    return st;
+}
+
 extern "C" {
 
 int32_t fwa_plan_get_i64(const fwa_plan *plan, const char *key, int64_t *value)
 {
     if (!plan || !key || !value) return fail(plan ? plan->ctx : nullptr, FWA_ERR_INVALID_ARG, "NULL argument");
     const std::string k(key);
-    const int64_t ng = plan->group ? (int64_t)((plan->batch + plan->group - 1) / plan->group) : 0;
+    const Pipeline &pl = plan->pipe;
+    const int64_t ng = pl.group ? (int64_t)((plan->batch + pl.group - 1) / pl.group) : 0;
     if (k == "batch") *value = (int64_t)plan->batch;
     else if (k == "fft_len") *value = plan->n;
     else if (k == "path") *value = plan->path;
-    else if (k == "group") *value = plan->group;
-    else if (k == "streams") *value = plan->n_streams;
+    else if (k == "group") *value = pl.group;
+    else if (k == "streams") *value = pl.n_streams;
     else if (k == "tile_w") *value = 16;   // one tile width ships (kept as a key: bench lines of every round carry it)
     else if (k == "xcd_swizzle") *value = plan->xcd_swizzle < 0 ? (int64_t)swizzle_default(plan) : plan->xcd_swizzle;
     else if (k == "depth") *value = plan->depth;
@@ -25,10 +44,10 @@ int32_t fwa_plan_get_i64(const fwa_plan *plan, const char *key, int64_t *value)
     else if (k == "device_error") {
         // bounded-spin timeout flag of the persistent kernel (0 in every healthy run); synchronises the device
         *value = 0;
-        if (plan->ring_ctl) {
+        if (pl.ctl) {
             uint32_t w = 0;
             HIP_TRY(plan->ctx, hipDeviceSynchronize());
-            HIP_TRY(plan->ctx, hipMemcpy(&w, plan->ring_ctl + 1, sizeof(w), hipMemcpyDeviceToHost));
+            HIP_TRY(plan->ctx, hipMemcpy(&w, pl.ctl + 1, sizeof(w), hipMemcpyDeviceToHost));
             *value = w;
         }
     }
@@ -42,8 +61,7 @@ int32_t fwa_plan_get_i64(const fwa_plan *plan, const char *key, int64_t *value)
     // other holders: cache + plans
     else if (k == "tables_shared") *value = plan->tb ? (int64_t)plan->tb.use_count() - 1 : 0;
     else if (k == "scratch_bytes")
-        *value = (int64_t)plan->ring_bytes + (plan->second_owned ? (int64_t)plan->own_second.bytes : 0) +
-                 (plan->ring_ctl ? (int64_t)ctl_bytes(plan) : 0);
+        *value = (int64_t)(pl.ring_bytes + pl.ctl_bytes) + (plan->second_owned ? (int64_t)plan->own_second.bytes : 0);
     else if (k == "launches_per_exec") {
         switch (plan->path) {
             case PATH_TWOPASS_1M: *value = 2 * ng; break;
@@ -65,18 +83,18 @@ int32_t fwa_plan_set_i64(fwa_plan *plan, const char *key, int64_t value)
     USE_DEVICE(ctx);
     const std::string k(key);
     if (k == "group" || k == "streams") {
-        if (plan->path != PATH_TWOPASS_1M && plan->path != PATH_TILED)
+        if (!is_pipelined(plan->path))
             return fail(ctx, FWA_ERR_UNSUPPORTED, "key only applies to the pipelined paths (2^20 two-pass, tiled)");
         if (value < 1 || value > (k == "streams" ? 16 : 4096))
             return fail(ctx, FWA_ERR_INVALID_ARG, "value out of range");
-        return build_pipeline(plan, k == "group" ? value : plan->group, k == "streams" ? value : plan->n_streams);
+        return build_pipeline(plan, k == "group" ? value : plan->pipe.group, k == "streams" ? value : plan->pipe.n_streams);
     }
     if (k == "inject_launch_failure") {
         // laboratory: the launch of group `value` fails once (nothing is enqueued for it): the error path of run_groups
         if (!kLab)
             return fail(ctx, FWA_ERR_UNSUPPORTED,
                         "inject_launch_failure is a laboratory knob (libfft_wgpu_amd_lab.so)");
-        if (plan->path != PATH_TWOPASS_1M && plan->path != PATH_TILED)
+        if (!is_pipelined(plan->path))
             return fail(ctx, FWA_ERR_UNSUPPORTED, "key only applies to the pipelined paths");
         plan->inject_fail_group = value;
         return FWA_OK;
@@ -86,11 +104,7 @@ int32_t fwa_plan_set_i64(fwa_plan *plan, const char *key, int64_t value)
         if (plan->path != PATH_TWOPASS_1M)
             return fail(ctx, FWA_ERR_UNSUPPORTED, "key only applies to the 2^20 two-pass path");
         if (value < 1 || value > 64) return fail(ctx, FWA_ERR_INVALID_ARG, "value out of range");
-        const int64_t old = plan->ring_rotate;
-        plan->ring_rotate = value;
-        const int32_t st = build_pipeline(plan, plan->group, plan->n_streams);
-        if (st) plan->ring_rotate = old;
-        return st;
+        return retune(plan, false, [&] { plan->ring_rotate = value; });
     }
     if (k == "tile_w") {
         if (plan->path != PATH_TWOPASS_1M)
@@ -104,16 +118,13 @@ int32_t fwa_plan_set_i64(fwa_plan *plan, const char *key, int64_t value)
             return fail(ctx, FWA_ERR_UNSUPPORTED, "key only applies to the persistent 2^20 path");
         if (value < 1 || value > 65536) return fail(ctx, FWA_ERR_INVALID_ARG, "value out of range");
         if (k == "wgs") { plan->wgs = value; return FWA_OK; }
-        const int64_t d = k == "depth" ? value : plan->depth, r = k == "ring_slots" ? value : plan->ring_slots;
-        if (k == "depth") { plan->depth = d; if (r < d + 1) plan->ring_slots = d + 1; }
-        else {
-            if (r < plan->depth + 1) return fail(ctx, FWA_ERR_INVALID_ARG, "ring_slots must exceed depth");
-            plan->ring_slots = r;
-        }
-        return build_pipeline(plan, 0, 0);
+        if (k == "depth")
+            return retune(plan, false, [&] { plan->depth = value; if (plan->ring_slots < value + 1) plan->ring_slots = value + 1; });
+        if (value < plan->depth + 1) return fail(ctx, FWA_ERR_INVALID_ARG, "ring_slots must exceed depth");
+        return retune(plan, false, [&] { plan->ring_slots = value; });
     }
     if (k == "xcd_swizzle") {
-        if (plan->path != PATH_TWOPASS_1M && plan->path != PATH_TILED)
+        if (!is_pipelined(plan->path))
             return fail(ctx, FWA_ERR_UNSUPPORTED, "key only applies to the pipelined paths");
         plan->xcd_swizzle = value & 7;
         return FWA_OK;
@@ -121,20 +132,16 @@ int32_t fwa_plan_set_i64(fwa_plan *plan, const char *key, int64_t value)
     if (k == "factors") {
         // re-factorise a multi-pass plan: value = log2(N1) | log2(N2) << 8 | log2(N3) << 16 (N3 = 0: two passes), every
         // factor a length its pass has a kernel for, product n.  A tuning knob: every factorisation computes the same transform.
-        if (plan->path != PATH_TILED && plan->path != PATH_TWOPASS_1M)
-            return fail(ctx, FWA_ERR_UNSUPPORTED, "key only applies to multi-pass plans");
+        if (!is_pipelined(plan->path)) return fail(ctx, FWA_ERR_UNSUPPORTED, "key only applies to multi-pass plans");
         const uint32_t f[3] = {(uint32_t)value & 255u, (uint32_t)(value >> 8) & 255u, (uint32_t)(value >> 16) & 255u};
         if (!factors_valid(plan->lg, f))
             return fail(ctx, FWA_ERR_INVALID_ARG, "every factor must be 2^6..2^10 (2^11: first; 2^11, 2^12: second of two)");
         if (f[0] + f[1] + f[2] != plan->lg || (value >> 24))
             return fail(ctx, FWA_ERR_INVALID_ARG, "factors do not multiply to fft_len");
-        const int64_t old_path = plan->path;
-        uint32_t old_lf[3] = {plan->lf[0], plan->lf[1], plan->lf[2]};
-        plan->path = PATH_TILED;
-        plan->lf[0] = f[0]; plan->lf[1] = f[1]; plan->lf[2] = f[2];
-        const int32_t st = setup_path(plan);
-        if (st) { plan->path = old_path; plan->lf[0] = old_lf[0]; plan->lf[1] = old_lf[1]; plan->lf[2] = old_lf[2]; }
-        return st;
+        return retune(plan, true, [&] {
+            plan->path = PATH_TILED;
+            plan->lf[0] = f[0]; plan->lf[1] = f[1]; plan->lf[2] = f[2];
+        });
     }
     if (k == "p1_gen" || k == "rows32" || k == "colsw" || k == "tile_ring") {
         if (plan->path != PATH_TILED) return fail(ctx, FWA_ERR_UNSUPPORTED, "key only applies to tiled plans");
@@ -160,14 +167,9 @@ int32_t fwa_plan_set_i64(fwa_plan *plan, const char *key, int64_t value)
             return fail(ctx, FWA_ERR_UNSUPPORTED, "path 5 is a laboratory path (libfft_wgpu_amd_lab.so)");
         if ((value == PATH_RING_1M || value == PATH_TWOPASS_1M)
             && (plan->path == PATH_RING_1M || plan->path == PATH_TWOPASS_1M)) {
-            // the two forms of the 2^20 pipeline: per-group launches with a large ring, or one persistent launch
-            const int64_t old = plan->path;
-            plan->path = value;
-            const int32_t st = setup_path(plan);
-            if (st) plan->path = old;
-            if (!st && value == PATH_TWOPASS_1M
-                && plan->ring_ctl) { (void)hipFree(plan->ring_ctl); plan->ring_ctl = nullptr; }
-            return st;
+            // the two forms of the 2^20 pipeline: per-group launches with a large ring, or one persistent launch (whose
+            // control words go with its pipeline when the plan switches back)
+            return retune(plan, true, [&] { plan->path = value; });
         }
         if (value == PATH_R2_GLOBAL && plan->n >= 2) {
             // force the literal reference recurrence (one launch per stage, kernel/fft.wgsl:27-62)
@@ -182,9 +184,7 @@ int32_t fwa_plan_set_i64(fwa_plan *plan, const char *key, int64_t value)
                 plan->own_second.bytes = plan->src->bytes;
                 plan->second_owned = true;
             }
-            Pipeline pl = take_pipeline(plan);
-            destroy_pipeline_objects(ctx, pl, true);
-            if (plan->ring_ctl) { (void)hipFree(plan->ring_ctl); plan->ring_ctl = nullptr; }
+            release_pipeline(ctx, plan->pipe, true);
             plan->path = PATH_R2_GLOBAL;
             return FWA_OK;
         }

@@ -6,11 +6,13 @@ inject_launch_failure.  They stay correct and, where they share arithmetic with 
 the product library rejects their keys.  (Round 6 removed L2 teams, the 32-column 2^20 tile, the LDS radix-2 and n < 16
 kernels, whose only loaders were the tests of this file: profiles/round6/lab_pruned_families.patch.)
 """
+import gc
+
 import numpy as np
 import pytest
 
 from conftest import REL_TOL  # noqa: F401
-from test_gpu_parity import _check, _fixture_sizes_body, _run
+from test_gpu_parity import _check, _fixture_sizes_body, _run, _upload
 
 pytestmark = pytest.mark.gpu
 
@@ -123,3 +125,44 @@ def test_failed_launch_mid_exec_still_joins_the_chains(gpu, oracle, n, batch, gr
     queue.write_buffer(src, 0, x, encoder=enc)
     z = plan.proc(enc).map_read(stream=enc)
     assert np.array_equal(z.view(np.uint64), ref.view(np.uint64))
+
+
+def test_path_round_trip_through_the_persistent_ring_leaves_a_plain_two_pass_plan(gpu, oracle):
+    """path 1 -> 5, depth = 2, ring_slots = 3, path 5 -> 1: the plan is a two-pass plan again -- the scratch of a fresh
+    one (no control words kept), its bits -- and once both plans are destroyed the device has its memory back up to the
+    rings the pool keeps.  2^20 x 4 (32 MiB) is the smallest batch that has path 1: below 4 transforms a 2^20 plan is
+    tiled (choose_path, FEW_1M) and the key "path" cannot reach 1 or 5."""
+    fw, dev, queue = gpu
+    n, batch = 1 << 20, 4
+    x = oracle.gen_input(n, batch, first_transform=13)
+    enc = dev.create_command_encoder()
+    bufs = [_upload(fw, dev, queue, x) for _ in range(2)]
+    for path in (1, 5):     # the context has its 2^20 tables and both kernel families loaded before memory is measured
+        warm = fw.Forward(dev, queue, bufs[0], n)
+        assert warm.get("path") == 1
+        warm.set("path", path)
+        warm.proc(enc)
+        enc.synchronize()
+        warm.destroy()
+    queue.write_buffer(bufs[0], 0, x)
+    gc.collect()            # buffers of earlier tests that only the collector frees (cycles through a caught exception) go now
+    before = dev.stats()
+    fresh, trip = (fw.Forward(dev, queue, b, n) for b in bufs)
+    for key, value in (("path", 5), ("depth", 2), ("ring_slots", 3)):
+        trip.set(key, value)
+        assert trip.get(key) == value
+    assert trip.get("scratch_bytes") > 3 * n * 8    # the ring of 3 transforms + the control words
+    trip.set("path", 1)
+    for key in ("path", "scratch_bytes", "group", "streams", "launches_per_exec", "device_error"):
+        assert trip.get(key) == fresh.get(key), key
+    assert fresh.get("path") == 1 and fresh.get("scratch_bytes") == batch * n * 8
+    y_fresh, y_trip = (p.proc(enc).map_read(stream=enc) for p in (fresh, trip))
+    assert np.array_equal(y_trip.view(np.uint64), y_fresh.view(np.uint64))
+    _check(oracle, y_fresh, oracle.dft_f64(x, n, -1), n)
+    fresh.destroy()
+    trip.destroy()
+    dev.poll()
+    after = dev.stats()
+    kept, pooled = before["mem_free_bytes"] - after["mem_free_bytes"], after["pooled_ring_bytes"] - before["pooled_ring_bytes"]
+    print("round trip 1 -> 5 -> 1: device memory kept %d bytes, ring pool grew by %d bytes" % (kept, pooled))
+    assert kept == pooled
