@@ -21,13 +21,31 @@ Rule, per case:
       transform, is held by the pin and by MAX_REL_CAP_FACTOR x cap(n).
 C = 1.05, chosen from the record so that the worst family sits at <= 0.8 of its cap: the three-pass tiled plans, whose
 k_tile passes multiply two-level twiddles (hi[e >> 10] * lo[e & 1023], tables.cpp upload_level) into one more rounded
-product, with rel_l2 / cap = 0.784 at 2^24 (rel_l2 2.40e-7; 2^20 x 1, 64 x 64 x 256: 0.775).  The worst max_rel sits
+product, with rel_l2 / cap = 0.784 at 2^24 (rel_l2 2.40e-7; 2^20 x 1, 64 x 64 x 256: 0.775).  C was chosen from the
+hand-picked rows and has not moved for the cell rows added since (below), all of which sit under the cap: the two-pass
+ones at 0.71-0.73, the three-pass ones at 0.74 (64 x 64 x 128), 0.79 (64 x 64 x 1024), 0.80 (64 x 1024 x 64) and 0.851
+(64 x 512 x 64, rel_l2 2.44e-7: the worst of the record).  k_tile at 512 and 1024 points has two twiddled radix-16 stages
+where 64 .. 256 points have one, and three such passes stack them; the error of those rows is the same to three digits
+in every transform and in all three plan kinds, and within 0.93-1.04 of the row's figure in each of 64 output blocks.
+The worst max_rel sits
 at 0.63 of MAX_REL_CAP_FACTOR x cap (k_chunk at n = 32: 1.66 x cap(32)).  For scale: a numpy fp32 radix-2 FFT with
 f32-rounded f64 twiddles sits at 0.55-0.58 of the cap (log2 n = 10..20), the same FFT with its twiddle angle evaluated
 in f32 at 1.12-1.58 (tests/test_error_budget.py); the flat 1e-5 sees neither.
 
+Which tiled rows there are is a rule, not a choice.  resolve_tiled (fft_wgpu_amd/csrc/schedule.h) picks the kernel of every
+pass from the length, the "factors" key, the flag keys "colsw" / "rows32" / "p1_gen" / "tile_ring" and the pass position;
+oracle/kernel_cells.py reads every such decision from tests/golden/tiled_schedule.txt and names its *cells*: pass A
+(kernel, log2 length, ring width), pass B (k_tile columns, log2 length), pass C (k_rows32, log2 length, ring width 0 / 32 / 64)
+or (k_tile rows, log2 length, two or three passes) -- 35 over 2^16 .. 2^28, each its own template instantiation per direction
+or its own branch on the slab layout or the pass count.  tests/test_kernel_cells.py demands that every cell is run by a row
+here in each of the three plan kinds, and that a tiled row's `kernels` text names the kernels its cells give.  The rows
+from _cell_row are the cells the hand-picked rows left out, each at the smallest (log2 n, factors, flag setting) that
+reaches it; they set "factors" and all four flags themselves, and run_case reads every key back.
+
 Out of the matrix on purpose: the 2^27..2^30 impulse test (tests/test_gpu_parity.py) keeps the flat bound; at those
-sizes a one-index twiddle error rotates by 2 pi / N <= 5e-8, below fp32 resolution.
+sizes a one-index twiddle error rotates by 2 pi / N <= 5e-8, below fp32 resolution.  With it stays what only a
+transform of >= 4 GiB (n >= 2^29) tells apart: the 64-bit-pointer form of k_tile (a tile spanning 2^32 bytes) and the four
+buffer descriptors of k_p1_gen, one per quarter of a transform, which below that size address what a single one would.
 """
 import hashlib
 import json
@@ -44,6 +62,7 @@ PIN_REL_L2 = 1.25
 PIN_MAX_REL = 1.5
 MAX_REL_CAP_FACTOR = 2.5
 MIN_SAMPLES = 1 << 18
+PATH_TILED = 7
 
 KINDS = (("Forward", -1), ("Inverse", 1), ("Onlyinverse", 1))
 
@@ -55,6 +74,16 @@ def _f(*lg):
 
 def _samples(n, batch=1):
     return max(batch, -(-MIN_SAMPLES // n))
+
+
+def _cell_row(name, lg, factors, flag_index, kernels):
+    """A tiled row that sets "factors" and all four flag keys itself (flag_index: bit 0 colsw, 1 rows32, 2 p1_gen, 3 tile_ring, as
+    schedule.h flag_setting), on at least two transforms so that the per-transform stride of every pass is exercised."""
+    n = 1 << lg
+    batch = _samples(n, 2)
+    tun = {"factors": _f(*factors)}
+    tun.update({key: flag_index >> i & 1 for i, key in enumerate(("colsw", "rows32", "p1_gen", "tile_ring"))})
+    return ("%sx%d" % (name, batch), n, batch, tun, (PATH_TILED, _f(*factors), len(factors)), kernels)
 
 
 # (id, n, batch, tunables, (path, factors, launches_per_exec), kernels).  Path 0: one launch (k_chunk up to 256, then
@@ -69,7 +98,7 @@ _CASES = (
         ("pipeline_2^20x4", 1 << 20, 4, {}, (1, _f(10, 10), 2), "k_p1_1m + k_p2_1m"),
         ("threepass_2^20x1", 1 << 20, 1, {}, (7, _f(6, 6, 8), 3), "k_tile x 3 (64 x 64 x 256)"),
         ("tile_2^16x4", 1 << 16, 4, {}, (7, _f(8, 8), 2), "latency regime: k_tile columns + k_tile rows"),
-        ("colsw_8_2^17x9", 1 << 17, 9, {}, (7, _f(8, 9), 2), "k_colsw<8,64> + k_rows32<9> (tile ring)"),
+        ("colsw_8_2^17x9", 1 << 17, 9, {}, (7, _f(8, 9), 2), "k_colsw<8,64> + k_rows32<9> (matrix layout: no tile ring for 512-point rows)"),
         ("colsw_9_2^19x3", 1 << 19, 3, {}, (7, _f(9, 10), 2), "k_colsw<9,32> + k_rows32<10> (tile ring)"),
         ("colsw0_2^19x3", 1 << 19, 3, {"colsw": 0}, (7, _f(9, 10), 2), "k_tile columns + k_rows32<10>"),
         ("colsw0_rows32_0_2^19x3", 1 << 19, 3, {"colsw": 0, "rows32": 0}, (7, _f(9, 10), 2),
@@ -88,6 +117,20 @@ _CASES = (
         ("tiled_2^25x1", 1 << 25, 1, {}, (7, _f(9, 8, 8), 3), "k_colsw<9,32> + k_tile columns + k_tile rows"),
         ("tiled_2^26x1", 1 << 26, 1, {}, (7, _f(9, 8, 9), 3), "k_colsw<9,32> + k_tile columns + k_tile rows"),
     ]
+    # the cells (oracle/kernel_cells.py) no row above runs, each at the smallest (log2 n, factors, flag setting) that reaches it
+    + [_cell_row(*r) for r in (
+        ("rows_tile_9_2^16", 16, (7, 9), 0, "k_tile columns + k_tile rows (512 points, two passes)"),
+        ("rows_tile_7_2^16", 16, (9, 7), 0, "k_tile columns + k_tile rows (128 points, two passes)"),
+        ("rows_tile_6_2^16", 16, (10, 6), 0, "k_tile columns + k_tile rows (64 points, two passes)"),
+        ("rows_tile_7_three_2^19", 19, (6, 6, 7), 0, "k_tile columns x 2 + k_tile rows (128 points, three passes)"),
+        ("ring64_2048_2^19", 19, (8, 11), 9, "k_colsw<8,64> + k_rows32<11> (tile ring 64)"),
+        ("ring64_4096_2^20", 20, (8, 12), 9, "k_colsw<8,64> + k_rows32<12> (tile ring 64)"),
+        ("ring32_2048_2^20", 20, (9, 11), 9, "k_colsw<9,32> + k_rows32<11> (tile ring 32)"),
+        ("mid_tile_9_2^21", 21, (6, 9, 6), 0, "k_tile columns x 2 (512-point middle pass) + k_tile rows"),
+        ("ring32_4096_2^21", 21, (9, 12), 9, "k_colsw<9,32> + k_rows32<12> (tile ring 32)"),
+        ("rows_tile_10_three_2^22", 22, (6, 6, 10), 0, "k_tile columns x 2 + k_tile rows (1024 points, three passes)"),
+        ("mid_tile_10_2^22", 22, (6, 10, 6), 0, "k_tile columns x 2 (1024-point middle pass) + k_tile rows"),
+    )]
 )
 
 # every case in each of the three transforming plan kinds; id "<case>/<kind>"
@@ -167,12 +210,14 @@ def run_case(fw, dev, queue, case, x):
     kind = case["kind"]
     plan = (fw.Onlyinverse(dev, queue, src, src2, n) if kind == "Onlyinverse"
             else getattr(fw, kind)(dev, queue, src, n))
-    for key, val in case["tunables"].items():   # "factors" first where both are given: it resets the group
-        if key == "factors":
-            plan.set(key, val)
-    for key, val in case["tunables"].items():
-        if key != "factors":
-            plan.set(key, val)
+    # "factors" first where both are given: it resets the group.  Every key is read back: a key the plan ignored or
+    # changed would run another kernel under this case's name.
+    for key, val in sorted(case["tunables"].items(), key=lambda kv: kv[0] != "factors"):
+        plan.set(key, val)
+        held = int(plan.get(key))
+        if held != val:
+            plan.destroy()
+            raise AssertionError("%s: set %s = %d, the plan holds %d" % (case["id"], key, val, held))
     enc = dev.create_command_encoder()
     out = plan.proc(enc)
     queue.submit(enc.finish())
