@@ -87,7 +87,7 @@ struct TileArgs {
 // blocks = batch*d1_count*tile_count
 hipError_t setup_tile_kernels();
 hipError_t launch_tile(int dir, int mode, uint32_t lg_l, const TileArgs &a, uint64_t batch, hipStream_t st);
-// k_p1_1m, k_p2_1m and k_p1_gen
+// k_p1_1m and k_p2_1m (tile_1m.h, kernels_1m.hip)
 hipError_t setup_1m_kernels();
 // One pass of the 2^20 pipeline over `n_transforms` transforms; transform i of the launch uses ring slot i
 // (1024 x 16-column tiles: 512-thread workgroups, 128-B segments).
@@ -96,11 +96,12 @@ hipError_t launch_p1_1m(int dir, const v2f *src, v2f *ring, const v2f *tw_inner,
 hipError_t launch_p2_1m(int dir, const v2f *ring, v2f *dst, const v2f *tw_inner, uint32_t n_transforms,
                         float scale, uint32_t xcd_swizzle, hipStream_t st);
 // 1024-point column pass for n = 1024 * pitch (pitch = 2^4 .. 2^20 columns), matrix layout in and out, four-step
-// twiddle of domain n from the two-level table (tw_lo, tw_hi); transform i at src + i*in_sb / dst + i*out_sb.
-// out_is_ring: the output is written through to the ring slab (the only form the library launches).
-hipError_t launch_p1_gen(int dir, bool out_is_ring, const v2f *src, v2f *dst, const v2f *tw_inner, const v2f *tw_lo,
-                         const v2f *tw_hi, uint32_t pitch, uint64_t in_sb, uint64_t out_sb, uint32_t n_transforms,
-                         uint32_t xcd_swizzle, hipStream_t st);
+// twiddle of domain n from the two-level table (tw_lo, tw_hi); transform i at src + i*in_sb / dst + i*out_sb; the output is
+// written through to the ring slab (kernels_p1_gen.hip: k_p1_gen)
+hipError_t setup_p1_gen_kernels();
+hipError_t launch_p1_gen(int dir, const v2f *src, v2f *dst, const v2f *tw_inner, const v2f *tw_lo, const v2f *tw_hi,
+                         uint32_t pitch, uint64_t in_sb, uint64_t out_sb, uint32_t n_transforms, uint32_t xcd_swizzle,
+                         hipStream_t st);
 hipError_t launch_scale(const v2f *a, v2f *b, uint64_t n_samples, float scale, hipStream_t st);
 hipError_t launch_fill(v2f *dst, uint64_t seed, uint64_t g0, uint64_t n_samples, float scale, hipStream_t st);
 hipError_t launch_copy(const void *src, void *dst, uint64_t bytes, hipStream_t st);

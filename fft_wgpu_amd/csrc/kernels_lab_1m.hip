@@ -44,12 +44,11 @@ __global__ __launch_bounds__(512, 4) void k_ring_1m(const v2f *src, v2f *dst, v2
                                                     const v2f *__restrict__ tw_outer, uint32_t *ctl, uint32_t batch,
                                                     uint32_t depth, uint32_t ring_slots, float scale)
 {
-    using G = Geom<16>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *xch = reinterpret_cast<float *>(smem);
-    v2f *twi = reinterpret_cast<v2f *>(smem + G::XCH_BYTES);
-    v2f *two = reinterpret_cast<v2f *>(smem + G::XCH_BYTES + G::TWI_BYTES);
-    uint32_t *s_next = reinterpret_cast<uint32_t *>(smem + G::XCH_BYTES + G::TWI_BYTES + G::TWO_BYTES);
+    v2f *twi = reinterpret_cast<v2f *>(smem + Geom::XCH_BYTES);
+    v2f *two = reinterpret_cast<v2f *>(smem + Geom::XCH_BYTES + Geom::TWI_BYTES);
+    uint32_t *s_next = reinterpret_cast<uint32_t *>(smem + Geom::XCH_BYTES + Geom::TWI_BYTES + Geom::TWO_BYTES);
     uint32_t *ticket = ctl, *err = ctl + 1, *done1 = ctl + RING_CTL_WORDS, *rdone = done1 + batch;
 
     reinterpret_cast<v4f *>(twi)[threadIdx.x] = reinterpret_cast<const v4f *>(tw_inner)[threadIdx.x];
@@ -88,14 +87,14 @@ __global__ __launch_bounds__(512, 4) void k_ring_1m(const v2f *src, v2f *dst, v2
                 if (tid == 0) spin_until_64(&rdone[t - ring_slots], err);
                 __syncthreads();
             }
-            p1_tile<DIR, 16>(src + (uint64_t)t * (1ull << 20), slab, tile, tw_outer + (size_t)tile * 1024, xch, twi, two, tid);
+            p1_tile<DIR>(src + (uint64_t)t * (1ull << 20), slab, tile, tw_outer + (size_t)tile * 1024, xch, twi, two, tid);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its write-through stores
             __syncthreads();
             if (tid == 0) __hip_atomic_fetch_add(&done1[t], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
             if (tid == 0) spin_until_64(&done1[t], err);
             __syncthreads();
-            p2_tile<DIR, 16, AUX_SC1>(slab, dst + (uint64_t)t * (1ull << 20), tile, scale, xch, twi, tid, [&] {
+            p2_tile<DIR, AUX_SC1>(slab, dst + (uint64_t)t * (1ull << 20), tile, scale, xch, twi, tid, [&] {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this tile's rows are in registers
                 __syncthreads();
                 if (tid == 0) __hip_atomic_fetch_add(&rdone[t], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -109,6 +108,19 @@ __global__ __launch_bounds__(512, 4) void k_ring_1m(const v2f *src, v2f *dst, v2
 
 size_t ring_ctl_bytes(uint64_t batch) { return sizeof(uint32_t) * (RING_CTL_WORDS + 2 * batch); }
 
+// Picker: the LDS of pass 1 plus the slot the next ticket is handed round in.
+static KernelLaunch ring_1m_launch(int dir)
+{
+    return {dir == FWD ? reinterpret_cast<const void *>(&k_ring_1m<FWD>) : reinterpret_cast<const void *>(&k_ring_1m<INV>),
+            Geom::THREADS, Geom::XCH_BYTES + Geom::TWI_BYTES + Geom::TWO_BYTES + 16};
+}
+
+hipError_t setup_lab_1m_kernels()
+{
+    hipError_t e = raise_lds_limit(ring_1m_launch(FWD));
+    return e == hipSuccess ? raise_lds_limit(ring_1m_launch(INV)) : e;
+}
+
 hipError_t launch_ring_1m(int dir, const v2f *src, v2f *dst, v2f *ring, const v2f *tw_inner, const v2f *tw_outer,
                           uint32_t *ctl, uint32_t batch, uint32_t depth, uint32_t ring_slots, uint32_t n_workgroups,
                           float scale, hipStream_t st)
@@ -120,22 +132,9 @@ hipError_t launch_ring_1m(int dir, const v2f *src, v2f *dst, v2f *ring, const v2
     hipError_t e = hipMemsetAsync(ctl, 0, ring_ctl_bytes(batch), st);
     if (e != hipSuccess) return e;
     if (n_workgroups > 128u * batch) n_workgroups = 128u * batch;
-    using G = Geom<16>;
+    const KernelLaunch k = ring_1m_launch(dir);
     void *args[] = {&src, &dst, &ring, &tw_inner, &tw_outer, &ctl, &batch, &depth, &ring_slots, &scale};
-    const void *k = dir == FWD ? reinterpret_cast<const void *>(&k_ring_1m<FWD>) : reinterpret_cast<const void *>(&k_ring_1m<INV>);
-    return hipLaunchKernel(k, dim3(n_workgroups), dim3(512), args, G::XCH_BYTES + G::TWI_BYTES + G::TWO_BYTES + 16, st);
-}
-
-hipError_t setup_lab_1m_kernels()
-{
-    hipError_t e = hipSuccess;
-    using G = Geom<16>;
-    const int lds = G::XCH_BYTES + G::TWI_BYTES + G::TWO_BYTES + 16;
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ring_1m<FWD>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ring_1m<INV>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    return e;
+    return hipLaunchKernel(k.kernel, dim3(n_workgroups), dim3(k.threads), args, k.lds, st);
 }
 
 }  // namespace fwa

@@ -17,7 +17,7 @@ namespace fwa_int {
 // launch one of them -- and only then: a plan of n <= 4096 loads no k_small32<14 / 15>.
 static hipError_t (*const kFamilySetups[])() = {
     fwa::setup_small32_kernels, fwa::setup_1m_kernels, fwa::setup_rows32_kernels, fwa::setup_colsw_kernels,
-    fwa::setup_cols32_kernels, fwa::setup_tile_kernels,
+    fwa::setup_cols32_kernels, fwa::setup_tile_kernels, fwa::setup_p1_gen_kernels,
 #ifdef FWA_LAB
     fwa::setup_lab_1m_kernels,
 #endif
@@ -178,7 +178,7 @@ struct TiledPass {
             case TiledKernel::COLS32:
                 return fwa::launch_cols32(dir, lg_l, in, out, tw, tw_lo, tw_hi, pitch, sb, sb, (uint32_t)cnt, swizzle, s);
             case TiledKernel::P1_GEN:
-                return fwa::launch_p1_gen(dir, true, in, out, tw_inner, tw_lo, tw_hi, pitch, sb, sb, (uint32_t)cnt, swizzle, s);
+                return fwa::launch_p1_gen(dir, in, out, tw_inner, tw_lo, tw_hi, pitch, sb, sb, (uint32_t)cnt, swizzle, s);
             case TiledKernel::ROWS32:
                 return fwa::launch_rows32(dir, lg_l, in, out, tw, n1, sb, sb, (uint32_t)cnt, scale, swizzle, ring_cw, s);
             case TiledKernel::TILE_COLS:

@@ -85,7 +85,7 @@ constexpr bool is_pipelined(int64_t path) { return path == PATH_TWOPASS_1M || pa
 
 // Kernel families, bit i set up by kFamilySetups[i] (plan.cpp): each raises the dynamic-LDS limits of its kernels (kernels.h),
 // once per context, before the first plan that may launch one of them.
-enum : uint32_t { FAM_SMALL32 = 1, FAM_1M = 2, FAM_ROWS32 = 4, FAM_COLSW = 8, FAM_COLS32 = 16, FAM_TILE = 32, FAM_LAB_RING = 64 };
+enum : uint32_t { FAM_SMALL32 = 1, FAM_1M = 2, FAM_ROWS32 = 4, FAM_COLSW = 8, FAM_COLS32 = 16, FAM_TILE = 32, FAM_P1_GEN = 64, FAM_LAB_RING = 128 };
 
 // ---- the tiled path (PATH_TILED): n = N1*N2[*N3] = 2^lf[0] * 2^lf[1] [* 2^lf[2]], pass A over N1, [B over N2,] C over the last ----
 // The keys of the same names (tuning.cpp); which of them takes effect is resolve_tiled's business alone.
@@ -97,7 +97,7 @@ struct TiledFlags {
 };
 
 enum class TiledKernel : uint8_t { NONE, COLSW, COLS32, P1_GEN, TILE_COLS, ROWS32, TILE_ROWS };
-constexpr uint32_t kFamilyOf[] = {0u, FAM_COLSW, FAM_COLS32, FAM_1M, FAM_TILE, FAM_ROWS32, FAM_TILE};  // by TiledKernel
+constexpr uint32_t kFamilyOf[] = {0u, FAM_COLSW, FAM_COLS32, FAM_P1_GEN, FAM_TILE, FAM_ROWS32, FAM_TILE};  // by TiledKernel
 
 struct TiledSchedule {
     TiledKernel a = TiledKernel::NONE, b = TiledKernel::NONE, c = TiledKernel::NONE;  // NONE for a, c: no kernel of that length

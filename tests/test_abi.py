@@ -43,9 +43,9 @@ def test_laboratory_library_has_the_same_abi_and_the_product_has_no_laboratory_k
         assert k not in prod, f"{k!r} found in the product library"
         assert k in labb, f"{k!r} missing from the laboratory library"
     # families removed in round 6 (profiles/round6/lab_pruned_families.patch) are in neither library
-    for k in (b"k_team", b"k_lds_small", b"k_tiny16", b"k_tiny2", b"k_p1_1mILin1ELi32E"):
+    for k in (b"k_team", b"k_lds_small", b"k_tiny16", b"k_tiny2", b"k_p1_1mILin1ELi32E", b"k_p1_genILin1ELi2E"):
         assert k not in prod and k not in labb, k
-    assert b"k_p1_1mILin1ELi16E" in prod and b"k_colsw" in prod and b"k_rows32" in prod
+    assert b"k_p1_1mILin1EE" in prod and b"k_colsw" in prod and b"k_rows32" in prod
     # only tools/ and the laboratory tests ask for the laboratory build
     hits = subprocess.run(["grep", "-rlE", r"lab=True|lab=args\.lab|LAB_LIB_PATH", "--include=*.py", ROOT],
                           capture_output=True, text=True).stdout.split()

@@ -15,8 +15,8 @@ template <int KO>
 __global__ __launch_bounds__(512) void k_p1_whatif(const v2f *__restrict__ src, v2f *__restrict__ ring, const v2f *__restrict__ tw_inner,
                                                    const v2f *__restrict__ tw_outer)
 {
-    constexpr int W = 16;
-    using G = Geom<W>;
+    using G = Geom;
+    constexpr int W = G::W;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *xch = reinterpret_cast<float *>(smem);
     v2f *twi = reinterpret_cast<v2f *>(smem + G::XCH_BYTES);
@@ -85,8 +85,8 @@ namespace fwa {
 template <int RD, int WR, int AUXW, int AUXR>
 __global__ __launch_bounds__(512) void k_skel(const v2f *__restrict__ src, v2f *__restrict__ ring)
 {
-    constexpr int W = 16;
-    using G = Geom<W>;
+    using G = Geom;
+    constexpr int W = G::W;
     const uint32_t tid = threadIdx.x;
     const uint32_t bid = xcd_block(1);
     const uint32_t tile = bid % G::TILES;
