@@ -23,7 +23,9 @@
  * groups of transforms on up to "streams" chain streams that belong to the
  * CONTEXT and are shared by all its plans: two plans executed on two caller
  * streams of one context therefore serialise on the chains (each exec still
- * forks from and joins to its own caller stream; results are unaffected).
+ * forks from and joins to its own caller stream; results are unaffected:
+ * tests/test_gpu_ordering.py runs it, and one plan on alternating caller
+ * streams, captured execs that fork, and a plan destroyed in flight).
  * Give concurrent pipelines their own context.  Streams this library creates
  * (the chains, fwa_stream_create) are checked to really overlap their peers
  * with ~40-us spin kernels at creation -- only when there is a peer to overlap

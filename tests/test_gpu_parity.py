@@ -1097,9 +1097,10 @@ def _hip_runtime():
 @pytest.mark.parametrize("n,batch", [(512, 2500), (1 << 20, 40), (1 << 18, 70), (1 << 22, 3)])
 def test_exec_captures_into_a_hip_graph(gpu, oracle, n, batch):
     """fwa_plan_exec is stream-ordered and allocates nothing, so a caller can capture it into a hipGraph (a HIP stream
-    of the caller's, wrapped with fwa_stream_wrap, captured in hipStreamCaptureModeGlobal) -- including the plans that
-    fork to internal streams and join back with events.  Replaying the graph on fresh input gives the bits of a direct
-    exec."""
+    of the caller's, wrapped with fwa_stream_wrap, captured in hipStreamCaptureModeGlobal).  Replaying the graph on fresh
+    input gives the bits of a direct exec.  All four shapes resolve to ONE chain (fewer than 4 groups: default_chains), so
+    their groups run on the caller's stream and nothing forks; the plans that fork to the chain streams and join back with
+    events are captured in tests/test_gpu_ordering.py (graph_forked/*)."""
     fw, dev, queue = gpu
     hip = _hip_runtime()
     x = oracle.gen_input(n, batch, first_transform=n % 89)

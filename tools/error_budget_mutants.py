@@ -2,9 +2,8 @@
 """tools/error_budget_mutants.py [build|run|all] [--only M1,M4] [--control] [--out FILE] -- evidence that the error budget
 (oracle/error_budget.py) catches twiddle errors the flat 1e-5 bound lets through.
 
-build: copy fft_wgpu_amd/csrc, objects included, to build/variants/<mutant>/csrc (as tools/build_variant.sh does), apply the
-       mutant's textual substitutions -- each must match exactly once, so the tool fails loudly when the source drifts --
-       and `make lab -j16`: only what depends on the mutated file is rebuilt.
+build: the copy-and-substitute build of tools/mutant_build.py: fft_wgpu_amd/csrc copied to build/variants/<mutant>/csrc, the
+       mutant's textual substitutions applied (each must match exactly once), `make lab`.
 run:   for each mutant, tools/record_error_budget.py --lab in a fresh child process with FWA_LAB_LIBRARY pointing at the
        mutant's laboratory library (under a time limit), then the budget's rule against the committed record.  One JSON
        line per mutant: worst max_rel / rel_l2 (and whether the old 1e-5 bound passes), the cases the budget rejects.
@@ -16,16 +15,13 @@ Every mutant is numerical only: it changes twiddle values, never an index into a
 import argparse
 import json
 import os
-import shutil
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import error_budget as eb  # noqa: E402
-
-VARIANTS = os.path.join(ROOT, "build", "variants")
-CSRC = os.path.join(ROOT, "fft_wgpu_amd", "csrc")
+from tools.mutant_build import TREE_LAB_LIBRARY, VARIANTS, build, lib_path  # noqa: E402
 
 # name: (what it models, [(file, old, new), ...])
 MUTANTS = {
@@ -47,35 +43,6 @@ MUTANTS = {
         ("cplx.h", "for (int i = 1; i < 12; ++i) { t *= -x2 / ((2 * i - 1) * (2 * i));",
          "for (int i = 1; i < 4; ++i) { t *= -x2 / ((2 * i - 1) * (2 * i));")]),
 }
-
-
-def lib_path(name):
-    return os.path.join(VARIANTS, name, "libfft_wgpu_amd_lab.so")
-
-
-def build(name):
-    dst = os.path.join(VARIANTS, name, "csrc")
-    shutil.rmtree(dst, ignore_errors=True)
-    os.makedirs(dst)
-    inc = os.path.join(VARIANTS, "include")       # csrc includes ../../include/fft_wgpu_amd.h
-    os.makedirs(inc, exist_ok=True)
-    for f in os.listdir(os.path.join(ROOT, "include")):
-        shutil.copy2(os.path.join(ROOT, "include", f), inc)
-    for f in os.listdir(CSRC):
-        if f.endswith(".so"):
-            continue
-        shutil.copy2(os.path.join(CSRC, f), dst)   # keeps mtimes: make rebuilds only what depends on the mutated file
-    for fname, old, new in MUTANTS[name][1]:
-        p = os.path.join(dst, fname)
-        src = open(p).read()
-        hits = src.count(old)
-        if hits != 1:
-            raise SystemExit("%s: substitution in %s matched %d times (expected exactly once): %r" % (name, fname, hits, old))
-        with open(p, "w") as f:
-            f.write(src.replace(old, new))
-    jobs = min(16, os.cpu_count() or 1)
-    subprocess.check_call(["make", "-s", "-C", dst, "-j%d" % jobs, "lab"])
-    print("%s: built %s" % (name, os.path.relpath(lib_path(name), ROOT)), flush=True)
 
 
 def run(name, lib, record, timeout):
@@ -127,11 +94,11 @@ def main():
     names = [m for m in args.only.split(",") if m] or list(MUTANTS)
     if args.what in ("build", "all"):
         for name in names:
-            build(name)
+            build(name, MUTANTS[name][1])
     if args.what == "build":
         return
     record = eb.load_record()
-    todo = ([("control", os.path.join(ROOT, "fft_wgpu_amd", "libfft_wgpu_amd_lab.so"))] if args.control else []) + \
+    todo = ([("control", TREE_LAB_LIBRARY)] if args.control else []) + \
         [(m, lib_path(m)) for m in names]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
