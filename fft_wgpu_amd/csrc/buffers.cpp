@@ -29,11 +29,8 @@ int32_t fwa_buf_alloc(fwa_ctx *ctx, uint64_t bytes, fwa_buf **out)
     }
     fwa_buf *b = new (std::nothrow) fwa_buf;
     if (!b) { (void)hipFree(p); return fail(ctx, FWA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
-    b->ctx = ctx; b->p = p; b->bytes = bytes; b->owned = true; b->device = ctx->device;
-    {
-        std::lock_guard<std::mutex> lk(ctx->live_mu);
-        ctx->live_bufs.insert(b);
-    }
+    b->p = p; b->bytes = bytes; b->owned = true; b->device = ctx->device;
+    attach(ctx, ctx->handles, b, H_BUF);  // links inside the handle: nothing is allocated, nothing can throw
     *out = b;
     return FWA_OK;
 }
@@ -45,11 +42,8 @@ int32_t fwa_buf_wrap(fwa_ctx *ctx, void *device_ptr, uint64_t bytes, fwa_buf **o
         return fail(ctx, FWA_ERR_INVALID_ARG, "device pointer must be 16-byte aligned");
     fwa_buf *b = new (std::nothrow) fwa_buf;
     if (!b) return fail(ctx, FWA_ERR_OUT_OF_MEMORY, "host allocation failed");
-    b->ctx = ctx; b->p = device_ptr; b->bytes = bytes; b->owned = false; b->device = ctx->device;
-    {
-        std::lock_guard<std::mutex> lk(ctx->live_mu);
-        ctx->live_bufs.insert(b);
-    }
+    b->p = device_ptr; b->bytes = bytes; b->owned = false; b->device = ctx->device;
+    attach(ctx, ctx->handles, b, H_BUF);
     *out = b;
     return FWA_OK;
 }
@@ -57,10 +51,7 @@ int32_t fwa_buf_wrap(fwa_ctx *ctx, void *device_ptr, uint64_t bytes, fwa_buf **o
 int32_t fwa_buf_free(fwa_buf *buf)
 {
     if (!buf) return FWA_OK;
-    if (buf->ctx) {
-        std::lock_guard<std::mutex> lk(buf->ctx->live_mu);
-        buf->ctx->live_bufs.erase(buf);
-    }
+    detach(buf);
     if (buf->owned && buf->p) { (void)hipSetDevice(buf->device); (void)hipFree(buf->p); }
     delete buf;
     return FWA_OK;

@@ -53,9 +53,15 @@ const char *thread_error_string() { return g_err.c_str(); }
 // streams are then taken as the runtime hands them out.
 bool any_stream_capturing(const fwa_ctx *ctx)
 {
-    for (const fwa_stream *s : ctx->live_streams) {
+    // the raw streams are copied out under the registry's lock (into room made before it) and asked afterwards
+    std::vector<hipStream_t> raws((size_t)count(ctx->handles, H_STREAM));
+    size_t n = 0;
+    for_each(ctx->handles, H_STREAM, [&](const Handle *h) {
+        if (n < raws.size()) raws[n++] = static_cast<const fwa_stream *>(h)->s;
+    });
+    for (size_t i = 0; i < n; ++i) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (s->s && hipStreamIsCapturing(s->s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return true;
+        if (raws[i] && hipStreamIsCapturing(raws[i], &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return true;
     }
     (void)hipGetLastError();
     return false;
@@ -262,12 +268,10 @@ int32_t fwa_ctx_destroy(fwa_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     for (auto &kv : ctx->free_rings) (void)hipFree(kv.second);
     for (auto s : ctx->chains) (void)hipStreamDestroy(s);
-    // stream handles that outlive their context (a garbage-collected host language frees in any order) stay destroyable
-    for (fwa_stream *st : ctx->live_streams) st->ctx = nullptr;
-    // ... and so do buffer and event handles: freed memory is never dereferenced through them, using one afterwards is
+    // stream, buffer and event handles that outlive their context (a garbage-collected host language frees in any order,
+    // from any thread) stay destroyable: freed memory is never dereferenced through them, using one afterwards is
     // FWA_ERR_INVALID_ARG (the device memory of an owned buffer is released by its own fwa_buf_free)
-    for (fwa_buf *b : ctx->live_bufs) b->ctx = nullptr;
-    for (fwa_event *ev : ctx->live_events) ev->ctx = nullptr;
+    detach_all(ctx->handles);
     ctx->tables.clear();
     delete ctx;
     return FWA_OK;
@@ -298,11 +302,8 @@ int32_t fwa_ctx_get_i64(const fwa_ctx *ctx, const char *key, int64_t *value)
     else if (k == "chain_pair_us") *value = ctx->chain_pair_us;
     else if (k == "chain_single_us") *value = ctx->chain_single_us;
     else if (k == "chain_check") *value = ctx->chain_check;
-    else if (k == "live_streams") *value = (int64_t)ctx->live_streams.size();
-    else if (k == "live_buffers") {
-        std::lock_guard<std::mutex> lk(const_cast<fwa_ctx *>(ctx)->live_mu);
-        *value = (int64_t)ctx->live_bufs.size();
-    }
+    else if (k == "live_streams") *value = (int64_t)count(ctx->handles, H_STREAM);
+    else if (k == "live_buffers") *value = (int64_t)count(ctx->handles, H_BUF);
     else if (k == "mem_free_bytes" || k == "mem_total_bytes") {
         int cur = -1;
         size_t fr = 0, tot = 0;
@@ -349,17 +350,20 @@ int32_t fwa_stream_create(fwa_ctx *ctx, fwa_stream **out)
     USE_DEVICE(ctx);
     // checked to overlap the (up to two) streams this context created most recently: a caller that makes a transfer
     // stream and a compute stream back to back gets two that really run side by side (overlapping_stream above)
-    hipStream_t s;
-    std::vector<hipStream_t> peers(ctx->user_streams.end() - (std::ptrdiff_t)std::min<size_t>(2,
-                                                                                              ctx->user_streams.size()),
-                                   ctx->user_streams.end());
+    // (wrappers, fwa_stream_wrap, are no peers: not even one of a stream that fwa_stream_create made)
+    hipStream_t s, last[2] = {nullptr, nullptr};
+    size_t n_owned = 0;
+    for_each(ctx->handles, H_STREAM, [&](const Handle *h) {
+        const fwa_stream *o = static_cast<const fwa_stream *>(h);
+        if (o->owned) { last[0] = last[1]; last[1] = o->s; ++n_owned; }
+    });
+    const std::vector<hipStream_t> peers(last + 2 - std::min<size_t>(2, n_owned), last + 2);
     int32_t rc = overlapping_stream(ctx, peers, &s);
     if (rc) return rc;
     fwa_stream *st = new (std::nothrow) fwa_stream;
     if (!st) { (void)hipStreamDestroy(s); return fail(ctx, FWA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
-    st->ctx = ctx; st->s = s; st->owned = true; st->device = ctx->device;
-    ctx->user_streams.push_back(s);
-    ctx->live_streams.push_back(st);
+    st->s = s; st->owned = true; st->device = ctx->device;
+    attach(ctx, ctx->handles, st, H_STREAM);  // links inside the handle: nothing is allocated, nothing can throw
     *out = st;
     return FWA_OK;
 }
@@ -369,8 +373,8 @@ int32_t fwa_stream_wrap(fwa_ctx *ctx, void *hip_stream, fwa_stream **out)
     if (!ctx || !out) return fail(ctx, FWA_ERR_INVALID_ARG, "ctx/out is NULL");
     fwa_stream *st = new (std::nothrow) fwa_stream;
     if (!st) return fail(ctx, FWA_ERR_OUT_OF_MEMORY, "host allocation failed");
-    st->ctx = ctx; st->s = reinterpret_cast<hipStream_t>(hip_stream); st->owned = false; st->device = ctx->device;
-    ctx->live_streams.push_back(st);
+    st->s = reinterpret_cast<hipStream_t>(hip_stream); st->owned = false; st->device = ctx->device;
+    attach(ctx, ctx->handles, st, H_STREAM);
     *out = st;
     return FWA_OK;
 }
@@ -387,14 +391,7 @@ int32_t fwa_stream_synchronize(fwa_stream *stream)
 int32_t fwa_stream_destroy(fwa_stream *stream)
 {
     if (!stream) return FWA_OK;
-    if (stream->ctx) {
-        auto &ls = stream->ctx->live_streams;
-        ls.erase(std::remove(ls.begin(), ls.end(), stream), ls.end());
-        // a wrapper (fwa_stream_wrap) of a handle fwa_stream_create made must not take the still-alive owned stream
-        // out of the overlap-check peer list
-        auto &us = stream->ctx->user_streams;
-        if (stream->owned) us.erase(std::remove(us.begin(), us.end(), stream->s), us.end());
-    }
+    detach(stream);
     if (stream->owned) {
         (void)hipSetDevice(stream->device);
         (void)hipStreamDestroy(stream->s);
@@ -427,11 +424,8 @@ int32_t fwa_event_create(fwa_ctx *ctx, fwa_event **out)
     HIP_TRY(ctx, hipEventCreate(&e));
     fwa_event *ev = new (std::nothrow) fwa_event;
     if (!ev) { (void)hipEventDestroy(e); return fail(ctx, FWA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
-    ev->ctx = ctx; ev->e = e;
-    {
-        std::lock_guard<std::mutex> lk(ctx->live_mu);
-        ctx->live_events.insert(ev);
-    }
+    ev->e = e;
+    attach(ctx, ctx->handles, ev, H_EVENT);
     *out = ev;
     return FWA_OK;
 }
@@ -472,10 +466,7 @@ int32_t fwa_event_elapsed_ms(fwa_event *start, fwa_event *end, float *ms)
 int32_t fwa_event_destroy(fwa_event *ev)
 {
     if (!ev) return FWA_OK;
-    if (ev->ctx) {
-        std::lock_guard<std::mutex> lk(ev->ctx->live_mu);
-        ev->ctx->live_events.erase(ev);
-    }
+    detach(ev);
     (void)hipEventDestroy(ev->e);
     delete ev;
     return FWA_OK;

@@ -5,6 +5,7 @@
 //   buffers.cpp      device / pinned memory, uploads, downloads, copies (peer copies across contexts), synthetic data
 //   tables.cpp       twiddle tables (reference twiddle rule src/processor.rs:43-49), the ring pool, build_pipeline /
 //                    release_pipeline: the only code that allocates or frees what a Pipeline (below) holds
+//   handles.h        which stream / buffer / event handles belong to which context, under one process-wide lock: no HIP
 //   schedule.h       path choice, kernel limits and the kernel of every pass of a tiled plan: pure integer logic, no HIP
 //   plan.cpp         plan create / destroy / exec (the four plan objects of src/processor.rs)
 //   tuning.cpp       fwa_plan_get_i64 / fwa_plan_set_i64; every key that rebuilds the pipeline goes through retune()
@@ -15,13 +16,12 @@
 #include <cstdint>
 #include <map>
 #include <memory>
-#include <mutex>
 #include <string>
 #include <tuple>
-#include <unordered_set>
 #include <vector>
 
 #include "../../include/fft_wgpu_amd.h"
+#include "handles.h"
 #include "kernels.h"
 
 using fwa::v2f;
@@ -83,35 +83,29 @@ struct fwa_ctx {
     // Internal chain streams of the pipelined paths: created once per context, shared by every plan, and checked at
     // creation to run kernels side by side (chain_streams() below).
     std::vector<hipStream_t> chains;
-    std::vector<hipStream_t> user_streams;  // alive streams made by fwa_stream_create, oldest first
-    std::vector<fwa_stream *> live_streams; // every alive fwa_stream handle of this context (created or wrapped)
     int64_t n_chain_checks = 0, n_chain_rejects = 0, chain_pair_us = 0, chain_single_us = 0;
     // fwa_ctx_set_i64("chain_check", 0): new streams are taken as the runtime hands them out
     int64_t chain_check = 1;
     std::vector<int> peers_enabled;         // device ordinals this context's device has peer access to (enabled once)
-    // Every alive fwa_buf / fwa_event handle of this context (allocated or wrapped).  fwa_ctx_destroy clears their `ctx`,
-    // as it does for streams, so that a handle which outlives its context (garbage-collected hosts free in any order)
-    // answers FWA_ERR_INVALID_ARG instead of dereferencing freed memory.  `live_mu` guards the two sets and the stream list
-    // below only: buffers may be allocated and freed from several threads of one context.
-    std::mutex live_mu;
-    std::unordered_set<fwa_buf *> live_bufs;
-    std::unordered_set<fwa_event *> live_events;
+    // Every alive fwa_stream / fwa_buf / fwa_event handle of this context (created, allocated or wrapped), oldest first.
+    // handles.h owns it and its lock; fwa_ctx_destroy detaches them all, so that a handle which outlives its context
+    // (garbage-collected hosts free in any order, from any thread) answers FWA_ERR_INVALID_ARG and stays destroyable.
+    fwa_int::HandleList handles;
 };
-struct fwa_stream {
-    fwa_ctx *ctx = nullptr;   // nullptr once the context has been destroyed (the handle can still be destroyed)
+// Handle::ctx is nullptr once the context has been destroyed: every entry point then refuses the handle, which can still
+// be destroyed (LIVE_HANDLE below).
+struct fwa_stream : fwa_int::Handle {
     hipStream_t s = nullptr;
     bool owned = false;
     int device = -1;
 };
-struct fwa_buf {
-    fwa_ctx *ctx = nullptr;   // nullptr once the context has been destroyed: every entry point then refuses the handle
+struct fwa_buf : fwa_int::Handle {
     void *p = nullptr;
     uint64_t bytes = 0;
     bool owned = false;
     int device = -1;          // for fwa_buf_free after the context is gone
 };
-struct fwa_event {
-    fwa_ctx *ctx = nullptr;   // nullptr once the context has been destroyed
+struct fwa_event : fwa_int::Handle {
     hipEvent_t e = nullptr;
 };
 
@@ -176,7 +170,8 @@ inline bool is_pow2(uint32_t n) { return n && !(n & (n - 1)); }
 inline hipStream_t raw(fwa_stream *s) { return s ? s->s : nullptr; }
 
 // A buffer / event handle whose context has been destroyed may still be freed, never used (include/fft_wgpu_amd.h,
-// "Lifetimes"): every entry point that takes one starts with this check.
+// "Lifetimes"): every entry point that takes one starts with this check.  A plain read outside the registry lock: only
+// FREEING a handle is safe while its context is being destroyed, using one concurrently stays the caller's error.
 #define LIVE_HANDLE(h, what)                                                                              \
     do {                                                                                                  \
         if (!(h)->ctx)                                                                                    \

@@ -273,9 +273,11 @@ int32_t fwa_plan_destroy(fwa_plan *plan)
         // only a stream that is known to be alive can take the marker: the null stream, or a stream of this context's
         // own making that has not been destroyed (HIP does not validate stream handles); otherwise the device-wide
         // wait below
-        const auto &us = plan->ctx->user_streams;
-        const bool alive = plan->last_stream == nullptr
-            || std::find(us.begin(), us.end(), plan->last_stream) != us.end();
+        bool alive = plan->last_stream == nullptr;
+        for_each(plan->ctx->handles, H_STREAM, [&](const Handle *h) {
+            const fwa_stream *s = static_cast<const fwa_stream *>(h);
+            alive = alive || (s->owned && s->s == plan->last_stream);
+        });
         if (plan->ran_on_stream && alive && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) {
             // everything this plan enqueued on its last caller stream precedes this marker
             if (hipEventRecord(ev, plan->last_stream) == hipSuccess) waited = hipEventSynchronize(ev) == hipSuccess;

@@ -16,6 +16,9 @@
  * `src/processor.rs:30-31`).
  *
  * Threading: ctx / plan creation and destruction are not thread-safe.
+ * Freeing or destroying buffer, stream and event handles (fwa_buf_free,
+ * fwa_stream_destroy, fwa_event_destroy) is safe from any thread, concurrently
+ * with one another and with fwa_ctx_destroy of their context (see Lifetimes).
  * One in-flight fwa_plan_exec per plan (plans own scratch).  One ctx per
  * device ordinal; multi-GPU = one process (or one ctx) per device: every
  * entry point makes its context's device current before it touches HIP.
@@ -36,7 +39,10 @@
  * Lifetimes: plans and communicators go before their context, buffers before the plans that use them.  Buffer, stream
  * and event HANDLES may be destroyed after their context (hosts with garbage collection free in any order): the context
  * keeps a list of its live handles and detaches them in fwa_ctx_destroy, so USING one afterwards -- upload, download,
- * copy, plan creation, event record ... -- returns FWA_ERR_INVALID_ARG; it never touches freed memory.
+ * copy, plan creation, event record ... -- returns FWA_ERR_INVALID_ARG; it never touches freed memory.  That list has one
+ * process-wide lock, so FREEING or DESTROYING such a handle is safe from any thread (finalizers run on their own): at the
+ * same time as other handles are freed and as fwa_ctx_destroy runs on its context.  Not safe for concurrent callers:
+ * creating a context, destroying one, and USING a handle while its context is being destroyed.
  *
  * Errors: every function returns an fwa_status (0 = ok).  Nothing aborts or
  * throws across the ABI.  fwa_last_error_string() gives detail.

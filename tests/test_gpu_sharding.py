@@ -292,6 +292,54 @@ def test_stream_and_buffer_handles_may_outlive_their_context(gpu, oracle):
     assert mx <= 1e-5
 
 
+def test_handles_freed_on_other_threads_while_their_context_is_destroyed(gpu, oracle):
+    """Finalizers of a garbage-collected host run on other threads (ctypes releases the GIL during a call): four threads free
+    64 buffer / event / stream handles through the raw ABI at the moment the main thread destroys their context.  Every call
+    answers 0 -- the registry of fft_wgpu_amd/csrc/handles.h orders them, tests/test_handles.py races it under sanitizers on
+    a CPU -- and the next launch on another context is unaffected.  Wrapped null streams only: a created stream would start
+    the spin kernels of the overlap check."""
+    import threading
+    fw, dev, queue = gpu
+    d = fw.Device(0)
+    L = d._L
+    owned = [d.create_buffer(4096) for _ in range(16)]
+    backing = d.create_buffer(4096)
+    views = [d.wrap_buffer(backing.device_ptr, 4096) for _ in range(16)]
+    events = [fw.Event(d) for _ in range(16)]
+    streams = []
+    for _ in range(16):
+        h = ctypes.c_void_p()
+        assert L.fwa_stream_wrap(d._h, None, ctypes.byref(h)) == 0
+        streams.append(h)
+    assert d.get("live_streams") == 17 and d.get("live_buffers") == 33
+    jobs = [(L.fwa_buf_free, b._h) for b in owned + views] + [(L.fwa_event_destroy, e._h) for e in events] \
+        + [(L.fwa_stream_destroy, s) for s in streams]
+    last, ctx = backing._h, d._h
+    for w in owned + views + events + [backing, d]:
+        w._h = None                              # keep the Python wrappers from freeing them first
+    d._default.destroy()
+    gate = threading.Barrier(5)
+    status = [[] for _ in range(4)]
+
+    def free_share(k):
+        gate.wait()
+        status[k] += [f(h) for f, h in jobs[k::4]]
+
+    threads = [threading.Thread(target=free_share, args=(k,)) for k in range(4)]
+    for t in threads:
+        t.start()
+    gate.wait()
+    destroyed = L.fwa_ctx_destroy(ctx)
+    for t in threads:
+        t.join()
+    assert destroyed == 0 and [len(s) for s in status] == [16] * 4 and not any(sum(status, []))
+    assert L.fwa_buf_free(last) == 0
+    x = oracle.gen_input(1024, 3)
+    y, _, _ = _run(fw, dev, queue, "Forward", x, 1024)
+    mx, _ = oracle.compare(y[:1024], oracle.dft_f64(x[:1024], 1024, -1))
+    assert mx <= 1e-5
+
+
 def test_using_a_handle_after_its_context_is_an_error_code_not_a_dangling_pointer(gpu, oracle):
     """ShardedBatch.destroy() destroys the contexts it created while the caller may still hold
     buffers, events and encoders on `sb.devices[i]`.  fwa_ctx_destroy detaches every live buffer / event / stream handle of the
