@@ -7,16 +7,11 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "kernels.h"  // v2f, FWD / INV: one definition for host and device
+
 namespace fwa {
 
-typedef float v2f __attribute__((ext_vector_type(2)));  // {re, im}: layout of reference src/lib.rs:10-15
 typedef float v4f __attribute__((ext_vector_type(4)));
-
-// Forward transforms use exp(-2*pi*i*k/n) (reference processor.rs:43-49); the
-// inverse uses the conjugate (ifft.wgsl:41-42).  Tables always hold the forward
-// value; DIR = +1 conjugates on use.
-constexpr int FWD = -1;
-constexpr int INV = +1;
 
 __device__ __forceinline__ v2f cmul(v2f a, v2f w)
 {

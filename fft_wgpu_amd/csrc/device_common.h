@@ -1,5 +1,6 @@
 // device_common.h -- device helpers shared by the kernel translation units (gfx950 only).
 #pragma once
+#include "cplx.h"
 #include "kernels.h"
 
 // Diagnostic hooks: empty in the library.  tools/archive/phase_probe.hip defines them before including a kernel source to
@@ -16,6 +17,30 @@
 #endif
 
 namespace fwa {
+
+// The grid rule of every launcher (after its early return for no work and its argument checks): at most 2^31 - 1 workgroups;
+// the XCD-aware block map (xcd_map below) needs a multiple of 8, any other grid runs unswizzled.
+inline hipError_t check_grid(uint64_t blocks, uint32_t *xcd_swizzle = nullptr)
+{
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    if (xcd_swizzle && blocks % 8) *xcd_swizzle = 0;
+    return hipSuccess;
+}
+
+// What a family's picker resolves (dir, sizes, variant) to: kernel (nullptr: no such variant), threads, dynamic LDS bytes.
+struct KernelLaunch {
+    const void *kernel = nullptr;
+    uint32_t threads = 0;
+    int lds = 0;
+};
+
+// More than the default 64 KiB of dynamic LDS needs a raised limit before the first launch: every setup_*_kernels() of
+// kernels.h does this for its family, once per context (plan.cpp: setup_path).
+inline hipError_t raise_lds_limit(const KernelLaunch &k)
+{
+    return k.kernel && k.lds > 65536 ? hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds)
+                                     : hipSuccess;
+}
 
 // Buffer (SRD) addressing: one 32-bit per-lane byte offset + a scalar offset per access, so the 32 loads
 // and 32 stores of a tile need no per-access VALU address math (cdna_hip_programming.md T8/T20).  The

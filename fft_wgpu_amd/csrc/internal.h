@@ -10,8 +10,12 @@
 //   plan.cpp         plan create / destroy / exec (the four plan objects of src/processor.rs)
 //   tuning.cpp       fwa_plan_get_i64 / fwa_plan_set_i64; every key that rebuilds the pipeline goes through retune()
 //   comm.cpp         fwa_comm_*: slab movement over RCCL
+//   kernels.h        the launch wrappers of kernels_*.hip: prototypes and argument structs, no device code
+// Nothing above includes a device header (cplx.h, device_common.h, tile_*.h, rows32.h, small32_*.h): the host files are
+// compiled once, as plain C++ against the HIP runtime API, and the same objects go into the product and the laboratory
+// library.
 #pragma once
-#include <hip/hip_runtime.h>
+#include <hip/hip_runtime_api.h>
 
 #include <cstdint>
 #include <map>
@@ -26,14 +30,14 @@
 
 using fwa::v2f;
 
-// FWA_LAB (libfft_wgpu_amd_lab.so, `make lab`): the same ABI plus the kernel families that measured slower than the
-// shipped ones -- path 5 (persistent 2^20 ring), small_reg = 2 / 3 (direct 16-point kernels, wavefront-shuffle exchange) --
-// and two test knobs (ring_rotate, inject_launch_failure).  The product library rejects those settings.
-#ifdef FWA_LAB
-constexpr bool kLab = true;
-#else
-constexpr bool kLab = false;
-#endif
+// The laboratory library (libfft_wgpu_amd_lab.so, `make lab`): the same ABI plus the kernel families that measured slower
+// than the shipped ones -- path 5 (persistent 2^20 ring), small_reg = 2 / 3 (direct 16-point kernels, wavefront-shuffle
+// exchange) -- and two test knobs (ring_rotate, inject_launch_failure).  The product library rejects those settings.
+// The two differ at link time only: the laboratory library links kernels_lab_*.hip (the laboratory launchers of kernels.h)
+// and lab_present.cpp (kLab = true), the product lab_absent.cpp (kLab = false and stubs of those launchers).  Plain
+// symbols, no table of function pointers: the host calls them by name like every other launcher, and fwa_plan_set_i64
+// refuses, when !kLab, every key that leads to one.
+using fwa::kLab;
 
 namespace fwa_int {
 

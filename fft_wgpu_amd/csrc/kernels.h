@@ -1,33 +1,22 @@
-// kernels.h -- launch wrappers implemented in kernels_*.hip (internal to the library).
+// kernels.h -- launch wrappers implemented in kernels_*.hip (internal to the library).  No device code: the host side
+// (internal.h) is plain C++ and sees the kernels only through these prototypes; what the launchers share among themselves
+// (check_grid, KernelLaunch, raise_lds_limit) is in device_common.h.
 #pragma once
-#include "cplx.h"
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+
 #include "schedule.h"  // the kernel limits (rows32_supported, colsw_width, ...): one definition for launchers and host
 
 namespace fwa {
 
-// The grid rule of every launcher (after its early return for no work and its argument checks): at most 2^31 - 1 workgroups;
-// the XCD-aware block map (xcd_map, device_common.h) needs a multiple of 8, any other grid runs unswizzled.
-inline hipError_t check_grid(uint64_t blocks, uint32_t *xcd_swizzle = nullptr)
-{
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    if (xcd_swizzle && blocks % 8) *xcd_swizzle = 0;
-    return hipSuccess;
-}
+typedef float v2f __attribute__((ext_vector_type(2)));  // {re, im}: layout of reference src/lib.rs:10-15
 
-// What a family's picker resolves (dir, sizes, variant) to: kernel (nullptr: no such variant), threads, dynamic LDS bytes.
-struct KernelLaunch {
-    const void *kernel = nullptr;
-    uint32_t threads = 0;
-    int lds = 0;
-};
-
-// More than the default 64 KiB of dynamic LDS needs a raised limit before the first launch: every setup_*_kernels() below does
-// this for its family, once per context (plan.cpp: setup_path).
-inline hipError_t raise_lds_limit(const KernelLaunch &k)
-{
-    return k.kernel && k.lds > 65536 ? hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds)
-                                     : hipSuccess;
-}
+// Forward transforms use exp(-2*pi*i*k/n) (reference processor.rs:43-49); the
+// inverse uses the conjugate (ifft.wgsl:41-42).  Tables always hold the forward
+// value; DIR = +1 conjugates on use.
+constexpr int FWD = -1;
+constexpr int INV = +1;
 
 hipError_t launch_r2_stage(int dir, const v2f *src, v2f *dst, const v2f *tw, uint32_t n, uint32_t stage,
                            uint64_t batch, float scale, hipStream_t st);
@@ -108,8 +97,9 @@ hipError_t launch_copy(const void *src, void *dst, uint64_t bytes, hipStream_t s
 // `blocks` one-wave workgroups that spin for ticks x 10 ns (<= 1 ms) without touching memory
 hipError_t launch_spin(uint32_t ticks, uint32_t blocks, hipStream_t st);
 
-#ifdef FWA_LAB
-// ---- laboratory build only (kernels_lab_*.hip): kernel families that measured slower than the shipped ones ----
+// ---- laboratory (kernels_lab_*.hip): kernel families that measured slower than the shipped ones.  The product library links
+// lab_absent.cpp in their place: kLab = false and stubs that no plan can reach (internal.h) ----
+extern const bool kLab;  // true in the library that holds the kernels below (lab_present.cpp)
 // 16 <= n <= 4096: register radix-16 Stockham with direct addressing (one launch); src == dst allowed (a transform is read
 // completely before any of it is written)
 // wave_shuffle: n = 32/64/128 exchange between the two stages with __shfl_xor instead of LDS (opt-in, slower)
@@ -122,6 +112,5 @@ hipError_t setup_lab_1m_kernels();  // k_ring_1m
 hipError_t launch_ring_1m(int dir, const v2f *src, v2f *dst, v2f *ring, const v2f *tw_inner, const v2f *tw_outer,
                           uint32_t *ctl, uint32_t batch, uint32_t depth, uint32_t ring_slots, uint32_t n_workgroups,
                           float scale, hipStream_t st);
-#endif
 
 }  // namespace fwa

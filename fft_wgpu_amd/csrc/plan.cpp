@@ -13,14 +13,13 @@ using namespace fwa_int;
 
 namespace fwa_int {
 
-// Kernel families (FAM_* of schedule.h), bit i set up by kFamilySetups[i], once per context, before the first plan that may
-// launch one of them -- and only then: a plan of n <= 4096 loads no k_small32<14 / 15>.
-static hipError_t (*const kFamilySetups[])() = {
-    fwa::setup_small32_kernels, fwa::setup_1m_kernels, fwa::setup_rows32_kernels, fwa::setup_colsw_kernels,
-    fwa::setup_cols32_kernels, fwa::setup_tile_kernels, fwa::setup_p1_gen_kernels,
-#ifdef FWA_LAB
-    fwa::setup_lab_1m_kernels,
-#endif
+// Kernel families (FAM_* of schedule.h), each set up once per context, before the first plan that may launch one of its
+// kernels -- and only then: a plan of n <= 4096 loads no k_small32<14 / 15>.  The order of the rows means nothing.
+static const struct { uint32_t family; hipError_t (*setup)(); const char *name; } kFamilySetups[] = {
+    {FAM_SMALL32, fwa::setup_small32_kernels, "small32"}, {FAM_1M, fwa::setup_1m_kernels, "1m"},
+    {FAM_ROWS32, fwa::setup_rows32_kernels, "rows32"},    {FAM_COLSW, fwa::setup_colsw_kernels, "colsw"},
+    {FAM_COLS32, fwa::setup_cols32_kernels, "cols32"},    {FAM_TILE, fwa::setup_tile_kernels, "tile"},
+    {FAM_P1_GEN, fwa::setup_p1_gen_kernels, "p1_gen"},    {FAM_LAB_RING, fwa::setup_lab_1m_kernels, "lab_ring"},
 };
 
 // The families a plan may launch on its path.  A tiled plan counts every kernel that the keys "colsw", "rows32", "p1_gen" and
@@ -48,11 +47,12 @@ int32_t setup_path(fwa_plan *p)
     fwa_ctx *ctx = p->ctx;
     const uint32_t fft_len = p->n;
     const uint32_t todo = path_families(p) & ~ctx->kernel_families;
-    for (uint32_t i = 0; i < std::size(kFamilySetups); ++i) {
-        if (!((todo >> i) & 1u)) continue;
-        hipError_t e = kFamilySetups[i]();
-        if (e != hipSuccess) return fail_hip(ctx, e, "hipFuncSetAttribute(max dynamic LDS)");
-        ctx->kernel_families |= 1u << i;
+    for (const auto &f : kFamilySetups) {
+        if (!(todo & f.family)) continue;
+        hipError_t e = f.setup();
+        if (e != hipSuccess)
+            return fail_hip(ctx, e, (std::string("hipFuncSetAttribute(max dynamic LDS), kernel family ") + f.name).c_str());
+        ctx->kernel_families |= f.family;
     }
     // tables: shared by every plan of this (length, path, factorisation) on the context
     const uint32_t sig = p->lf[0] | (p->lf[1] << 8) | (p->lf[2] << 16);
@@ -122,9 +122,8 @@ static int32_t run_groups(fwa_plan *plan, hipStream_t st, Body body)
     for (uint64_t g = 0; g < n_groups && e == hipSuccess; ++g) {
         const size_t c = ns ? (size_t)(g % ns) : 0;
         const uint64_t cnt = (plan->batch - g * G < G) ? plan->batch - g * G : G;
-#ifdef FWA_LAB
+        // laboratory knob "inject_launch_failure" (-1, never equal, in the product library: tuning.cpp)
         if (plan->inject_fail_group == (int64_t)g) { plan->inject_fail_group = -1; e = hipErrorLaunchFailure; break; }
-#endif
         e = body(g, cnt, ns ? pl.streams[c] : st, c);
     }
     // Join the chains back to the caller's stream ALSO when a launch failed: the groups enqueued before the failure
@@ -416,14 +415,12 @@ int32_t fwa_plan_exec(fwa_plan *plan, fwa_stream *stream, fwa_buf **result)
             if (scale != 1.0f) e = fwa::launch_scale(a, a, total, scale, st);
             break;
         case PATH_SMALL:
-#ifdef FWA_LAB
             // laboratory kernels (A/B): the direct 16-point kernels (small_reg = 3, 16 <= n <= 4096), with the
             // wavefront-shuffle exchange at 32 / 64 / 128 (small_reg = 2, which leaves n >= 512 to k_small32)
-            if (plan->small_reg != 1 && plan->n >= 16 && plan->n <= 4096 && (plan->small_reg == 3 || plan->n < 512)) {
+            if (kLab && plan->small_reg != 1 && plan->n >= 16 && plan->n <= 4096 && (plan->small_reg == 3 || plan->n < 512)) {
                 e = fwa::launch_small16(dir, a, out, tb.tw_half, plan->n, plan->batch, scale, plan->small_reg == 2, st);
                 break;
             }
-#endif
             if (plan->n <= 256)
                 e = fwa::launch_chunk(dir, a, out, tb.tw_half, plan->n, plan->batch, scale, st);
             else
@@ -454,8 +451,8 @@ int32_t fwa_plan_exec(fwa_plan *plan, fwa_stream *stream, fwa_buf **result)
                 return fwa::launch_p2_1m(dir, slab, out + g * G * N, tb.tw_inner, (uint32_t)cnt, scale, swz, s);
             });
         }
-#ifdef FWA_LAB
         case PATH_RING_1M: {
+            if (!kLab) return fail(ctx, FWA_ERR_UNSUPPORTED, "plan path not implemented");
             if (!pl.ring || !pl.ctl)
                 return fail(ctx, FWA_ERR_INVALID_ARG, "plan has no scratch ring (a failed re-tune?)");
             const uint64_t slots = (uint64_t)plan->ring_slots < plan->batch ? (uint64_t)plan->ring_slots : plan->batch;
@@ -466,7 +463,6 @@ int32_t fwa_plan_exec(fwa_plan *plan, fwa_stream *stream, fwa_buf **result)
                                         (uint32_t)plan->wgs, scale, st);
             break;
         }
-#endif
         case PATH_TILED: {
             // Per group of transforms: pass A, user buffer -> ring slab; [pass B, in place in the slab]; pass C, slab ->
             // result buffer (src for even log2 n -- in place at group granularity -- else second).  The kernels are

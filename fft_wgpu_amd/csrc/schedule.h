@@ -83,8 +83,8 @@ inline int64_t choose_path(uint32_t n, uint64_t batch, uint32_t lf[3], bool *col
 // The paths that run groups of transforms through a scratch ring, over chains (keys "group", "streams", "xcd_swizzle").
 constexpr bool is_pipelined(int64_t path) { return path == PATH_TWOPASS_1M || path == PATH_TILED; }
 
-// Kernel families, bit i set up by kFamilySetups[i] (plan.cpp): each raises the dynamic-LDS limits of its kernels (kernels.h),
-// once per context, before the first plan that may launch one of them.
+// Kernel families, one bit each, paired with their setup functions in kFamilySetups (plan.cpp): each raises the dynamic-LDS
+// limits of its kernels (kernels.h), once per context, before the first plan that may launch one of them.
 enum : uint32_t { FAM_SMALL32 = 1, FAM_1M = 2, FAM_ROWS32 = 4, FAM_COLSW = 8, FAM_COLS32 = 16, FAM_TILE = 32, FAM_P1_GEN = 64, FAM_LAB_RING = 128 };
 
 // ---- the tiled path (PATH_TILED): n = N1*N2[*N3] = 2^lf[0] * 2^lf[1] [* 2^lf[2]], pass A over N1, [B over N2,] C over the last ----

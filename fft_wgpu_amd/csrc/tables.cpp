@@ -144,8 +144,7 @@ int32_t build_pipeline(fwa_plan *p, int64_t group, int64_t n_streams)
         release_pipeline(ctx, pl, st == FWA_OK);   // the old pipeline on success, else the unfinished new one
         return st;
     };
-#ifdef FWA_LAB
-    if (p->path == PATH_RING_1M) {
+    if (kLab && p->path == PATH_RING_1M) {
         // one launch, no internal streams: ring of min(ring_slots, batch) transforms + the control words
         const uint64_t slots = (uint64_t)p->ring_slots < p->batch ? (uint64_t)p->ring_slots : p->batch;
         pl.group = p->pipe.group; pl.n_streams = p->pipe.n_streams;
@@ -158,7 +157,6 @@ int32_t build_pipeline(fwa_plan *p, int64_t group, int64_t n_streams)
         }
         return finish(FWA_OK);
     }
-#endif
     if (!is_pipelined(p->path)) return FWA_OK;
     if (group < 1) group = 1;
     if ((uint64_t)group > p->batch && p->batch) group = (int64_t)p->batch;

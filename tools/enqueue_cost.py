@@ -2,6 +2,8 @@
 """Host cost of enqueueing one exec, and of ONE process driving several devices.
 
     python tools/enqueue_cost.py > profiles/round5/enqueue_cost.jsonl
+    python tools/enqueue_cost.py --lib build/variants/parent/libfft_wgpu_amd.so     (leg 1 only, on that build: an A/B of two
+                                                                                     libraries alternates such calls)
 
 Leg 1: one context, the C3 shape (N = 2^20 x 4096, 32 GiB): wall time for `fwa_plan_exec` (through `Forward.proc`) to
 RETURN -- 512 kernel launches, 2 x 256 event record / wait pairs, nothing waited for -- on an idle queue.
@@ -11,6 +13,7 @@ side: a launch costs the host the same whichever device it goes to.  The shards 
 columns are NOT a multi-GPU figure; the "returns" columns are the point: if 8 x the per-device host time approaches one
 device's GPU time (21 ms at C3), serial enqueue makes an 8-GPU process host-bound.
 """
+import argparse
 import json
 import os
 import statistics
@@ -25,8 +28,8 @@ import fft_wgpu_amd as fw  # noqa: E402
 N = 1 << 20
 
 
-def leg_one_context(batch=4096, reps=8):
-    dev, queue = fw.prepare_gpu(0)
+def leg_one_context(batch=4096, reps=8, lib=None):
+    dev, queue = fw.prepare_gpu(0, lab=os.path.abspath(lib) if lib else False)
     buf = dev.create_buffer(N * batch * 8)
     plan = fw.Forward(dev, queue, buf, N)
     enc = dev.create_command_encoder()
@@ -43,7 +46,8 @@ def leg_one_context(batch=4096, reps=8):
             ret.append((t1 - t0) * 1e3)
             done.append((t2 - t0) * 1e3)
     launches = plan.get("launches_per_exec")
-    print(json.dumps({"host": "python", "what": "Forward.proc (fwa_plan_exec), one context", "fft_len": N, "batch": batch,
+    print(json.dumps({"host": "python", "what": "Forward.proc (fwa_plan_exec), one context", "lib": lib or "product",
+                      "fft_len": N, "batch": batch,
                       "launches": launches, "chains": plan.get("streams"), "returns_ms_median": statistics.median(ret),
                       "returns_ms_min": min(ret), "returns_us_per_launch": statistics.median(ret) * 1e3 / launches,
                       "done_ms_median": statistics.median(done), "reps": reps}), flush=True)
@@ -88,6 +92,12 @@ def leg_cpp(shards, per):
 
 
 if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lib", help="leg 1 only, on this build of the library")
+    args = ap.parse_args()
+    if args.lib:
+        leg_one_context(lib=args.lib)
+        sys.exit(0)
     leg_one_context()
     for per in (64, 512):
         leg_sharded(8, per)
