@@ -133,6 +133,16 @@ _CASES = (
     )]
 )
 
+pack_factors, samples = _f, _samples      # the public names, for the modules that build rows of their own
+
+
+def case_row(name):
+    """The row `name` of _CASES by field, for modules that derive rows from it (oracle/special_values.py): a change of the
+    tuple's shape is then made here once."""
+    cid, n, batch, tunables, (path, factors, passes), kernels = next(c for c in _CASES if c[0] == name)
+    return dict(case=cid, n=n, batch=batch, tunables=dict(tunables), path=path, factors=factors, passes=passes, kernels=kernels)
+
+
 # every case in each of the three transforming plan kinds; id "<case>/<kind>"
 MATRIX = [dict(id="%s/%s" % (c[0], kind), case=c[0], kind=kind, direction=direction, n=c[1], batch=c[2],
                tunables=c[3], path=c[4][0], factors=c[4][1], launches_per_exec=c[4][2], kernels=c[5])
