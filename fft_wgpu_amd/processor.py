@@ -58,6 +58,26 @@ class _Plan:
         _ffi.check(self.device._L.fwa_plan_set_i64(self._h, key.encode(), int(value)), self.device._h,
                    "fwa_plan_set_i64", self.device._L)
 
+    def configure(self, tunables, verify=True):
+        """Set the tuning keys of ``tunables`` in PLAN_KEYS order (a value of None leaves its key alone) and read each one
+        back -> {key: value the plan holds}.  A key outside PLAN_KEYS raises before anything is set; with ``verify`` a key
+        the plan clamped or ignored raises too.  "inject_launch_failure" has no getter: set, not read back."""
+        unknown = sorted(set(tunables) - set(PLAN_KEYS))
+        if unknown:
+            raise ValueError("unknown plan keys: %s" % ", ".join(unknown))
+        held = {}
+        for key in PLAN_KEYS:
+            value = tunables.get(key)
+            if value is None:
+                continue
+            self.set(key, value)
+            if key == "inject_launch_failure":
+                continue
+            held[key] = int(self.get(key))
+            if verify and held[key] != int(value):
+                raise ValueError("set %s = %d, the plan holds %d" % (key, int(value), held[key]))
+        return held
+
     def destroy(self):
         if self._h:
             self.device._L.fwa_plan_destroy(self._h)
@@ -100,3 +120,15 @@ class Normalize(_Plan):
 
     def __init__(self, device, queue, buffer1, buffer2, fft_len):
         super().__init__(device, queue, buffer1, buffer2, fft_len)
+
+
+SECOND_BUFFER_KINDS = ("Onlyinverse", "Normalize")      # the kinds whose second buffer is the caller's
+
+
+def plan_of_kind(kind, device, queue, src, src2, fft_len):
+    """The plan class named ``kind`` ("Forward", "Inverse", "Onlyinverse", "Normalize") on ``src`` and, for the kinds of
+    SECOND_BUFFER_KINDS, ``src2``."""
+    cls = {"Forward": Forward, "Inverse": Inverse, "Onlyinverse": Onlyinverse, "Normalize": Normalize}[kind]
+    if kind in SECOND_BUFFER_KINDS:
+        return cls(device, queue, src, src2, fft_len)
+    return cls(device, queue, src, fft_len)

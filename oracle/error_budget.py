@@ -40,7 +40,7 @@ or (k_tile rows, log2 length, two or three passes) -- 35 over 2^16 .. 2^28, each
 or its own branch on the slab layout or the pass count.  tests/test_kernel_cells.py demands that every cell is run by a row
 here in each of the three plan kinds, and that a tiled row's `kernels` text names the kernels its cells give.  The rows
 from _cell_row are the cells the hand-picked rows left out, each at the smallest (log2 n, factors, flag setting) that
-reaches it; they set "factors" and all four flags themselves, and run_case reads every key back.
+reaches it; they set "factors" and all four flags themselves, and device_run.run reads every key back.
 
 Out of the matrix on purpose: the 2^27..2^30 impulse test (tests/test_gpu_parity.py) keeps the flat bound; at those
 sizes a one-index twiddle error rotates by 2 pi / N <= 5e-8, below fp32 resolution.  With it stays what only a
@@ -52,6 +52,8 @@ import json
 import os
 
 import numpy as np
+
+from .device_run import blocks, run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RECORD_PATH = os.path.join(ROOT, "tests", "golden", "error_budget.json")
@@ -154,25 +156,19 @@ def cap(n):
 
 
 def metrics(y, r, n):
-    """(rel_l2 over the batch, worst per-transform max_rel) of complex64 `y` against complex128 `r`, in blocks."""
-    y = np.asarray(y).reshape(-1, n)
-    r = np.asarray(r).reshape(-1, n)
-    batch = y.shape[0]
+    """(rel_l2 over the batch, worst per-transform max_rel) of complex64 `y` against complex128 `r`, over
+    device_run.blocks."""
+    batch = np.size(y) // n
     maxd = np.zeros(batch)
     maxr = np.zeros(batch)
     sd = sr = 0.0
-    rows = max(1, (1 << 22) // n)
-    cols = min(n, 1 << 22)
-    for t0 in range(0, batch, rows):
-        for k0 in range(0, n, cols):
-            yb = y[t0:t0 + rows, k0:k0 + cols].astype(np.complex128)
-            rb = r[t0:t0 + rows, k0:k0 + cols]
-            d = np.abs(yb - rb)
-            m = np.abs(rb)
-            maxd[t0:t0 + rows] = np.maximum(maxd[t0:t0 + rows], d.max(axis=1))   # NaN-propagating
-            maxr[t0:t0 + rows] = np.maximum(maxr[t0:t0 + rows], m.max(axis=1))
-            sd += float((d * d).sum())
-            sr += float((m * m).sum())
+    for t0, diff, rb in blocks(y, r, n):
+        t = slice(t0, t0 + diff.shape[0])
+        d, m = np.abs(diff), np.abs(rb)
+        maxd[t] = np.maximum(maxd[t], d.max(axis=1))   # NaN-propagating
+        maxr[t] = np.maximum(maxr[t], m.max(axis=1))
+        sd += float((d * d).sum())
+        sr += float((m * m).sum())
     rel_l2 = np.sqrt(sd / sr) if sr > 0 else np.sqrt(sd)
     return float(rel_l2), float(np.max(maxd / np.where(maxr > 0, maxr, 1.0)))
 
@@ -211,35 +207,6 @@ def kernel_source_sha256(root=ROOT):
     return h.hexdigest()
 
 
-def run_case(fw, dev, queue, case, x):
-    """One exec of the case's plan on input `x` (complex64, n * batch) -> (y, plan facts)."""
-    n = case["n"]
-    src = dev.create_buffer(x.nbytes)
-    queue.write_buffer(src, 0, x)
-    src2 = dev.create_buffer(x.nbytes) if case["kind"] == "Onlyinverse" else None
-    kind = case["kind"]
-    plan = (fw.Onlyinverse(dev, queue, src, src2, n) if kind == "Onlyinverse"
-            else getattr(fw, kind)(dev, queue, src, n))
-    # "factors" first where both are given: it resets the group.  Every key is read back: a key the plan ignored or
-    # changed would run another kernel under this case's name.
-    for key, val in sorted(case["tunables"].items(), key=lambda kv: kv[0] != "factors"):
-        plan.set(key, val)
-        held = int(plan.get(key))
-        if held != val:
-            plan.destroy()
-            raise AssertionError("%s: set %s = %d, the plan holds %d" % (case["id"], key, val, held))
-    enc = dev.create_command_encoder()
-    out = plan.proc(enc)
-    queue.submit(enc.finish())
-    y = out.map_read(stream=enc)
-    facts = {k: int(plan.get(k)) for k in ("path", "factors", "launches_per_exec")}
-    plan.destroy()
-    for b in (src, src2):
-        if b is not None:
-            b.destroy()
-    return y, facts
-
-
 def measure(fw, dev, queue, cases=None, log=None):
     """Run `cases` (default MATRIX) -> {id: {rel_l2, max_rel, path, factors, launches_per_exec}}.  The fp64 DFT of a
     (case, direction) is computed once and shared by Inverse and Onlyinverse."""
@@ -255,7 +222,7 @@ def measure(fw, dev, queue, cases=None, log=None):
             x = oracle.gen_input(n, batch)
             memo[key] = (x, oracle.dft_f64(x, n, case["direction"]))
         x, r = memo[key]
-        y, facts = run_case(fw, dev, queue, case, x)
+        y, _, facts = run(fw, dev, queue, case["kind"], x, n, case["tunables"])
         rr = r / n if case["kind"] == "Inverse" else r
         rel_l2, max_rel = metrics(y, rr, n)
         out[case["id"]] = dict(rel_l2=rel_l2, max_rel=max_rel, **facts)

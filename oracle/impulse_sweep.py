@@ -68,6 +68,7 @@ import numpy as np
 
 from . import error_budget as eb
 from . import special_values as sv
+from .device_run import execute, planned
 
 ROOT = eb.ROOT
 RECORD_PATH = os.path.join(ROOT, "tests", "golden", "impulse_response.json")
@@ -287,34 +288,15 @@ def load_record(path=RECORD_PATH):
 def run_case(fw, dev, queue, case):
     """One (row, kind) through the C ABI -> dict(worst, t, k, p, compared, path, factors, tunables read back)."""
     n, kind = case["n"], case["kind"]
-    nbytes = buffer_transforms(case) * n * 8
-    src = dev.create_buffer(nbytes)
-    src2 = dev.create_buffer(nbytes) if kind == "Onlyinverse" else None
-    plan = fw.Onlyinverse(dev, queue, src, src2, n) if kind == "Onlyinverse" else getattr(fw, kind)(dev, queue, src, n)
-    enc = dev.create_command_encoder()
     one = np.ones(1, dtype=np.complex64)
-    try:
-        held = {}
-        for key, val in sorted(case["tunables"].items(), key=lambda kv: kv[0] != "factors"):
-            plan.set(key, val)
-            held[key] = int(plan.get(key))
-            if held[key] != val:
-                raise AssertionError("%s: set %s = %d, the plan holds %d" % (case["id"], key, val, held[key]))
-
-        def run_chunk(p):
-            dev.fill_synthetic(src, n, scale=0.0, encoder=enc)
-            for j, pj in enumerate(p):
-                queue.write_buffer(src, (j * n + int(pj)) * 8, one, encoder=enc)
-            out = plan.proc(enc)
-            queue.submit(enc.finish())
-            return lambda first, count: out.map_read(first * 8, count * 8, enc)
+    with planned(fw, dev, queue, kind, n, buffer_transforms(case) * n * 8, case["tunables"]) as p:
+        def run_chunk(pos):
+            dev.fill_synthetic(p.src, n, scale=0.0, encoder=p.enc)
+            for j, pj in enumerate(pos):
+                queue.write_buffer(p.src, (j * n + int(pj)) * 8, one, encoder=p.enc)
+            out, _ = execute(p)
+            return lambda first, count: out.map_read(first * 8, count * 8, p.enc)
 
         got = sweep(case, kind, run_chunk)
-        got.update(path=int(plan.get("path")), factors=int(plan.get("factors")), tunables=held)
-    finally:
-        plan.destroy()
-        for b in (src, src2):
-            if b is not None:
-                b.destroy()
-        enc.destroy()
+        got.update(path=int(p.plan.get("path")), factors=int(p.plan.get("factors")), tunables=p.held)
     return got

@@ -26,12 +26,12 @@ import ctypes
 
 import numpy as np
 
+from .device_run import hip_runtime, parity_failures, upload
 from .error_budget import _f
 
 REL_TOL = 1e-5            # the parity bound of the suite (tests/conftest.py REL_TOL; tests/test_ordering.py compares them)
 POISON = 0x7FC0DEAD       # a quiet NaN as f32: a destination nobody wrote stays recognisable
 DIRECTION = {"Forward": -1, "Inverse": 1, "Onlyinverse": 1, "Onlyinverse+Normalize": 1}
-KEY_ORDER = ("factors", "group", "streams")   # "factors" re-plans the pipeline, so it comes first
 
 # tag -> n, batch, keys set before the first exec, and what the plan must then report
 SHAPES = {
@@ -82,25 +82,16 @@ def make_plan(fw, dev, queue, tag, kind, src, src2=None, tunables=None, want=Non
     s = SHAPES[tag]
     tunables = s["tunables"] if tunables is None else tunables
     want = s["want"] if want is None else want
-    if kind == "Onlyinverse":
-        plan = fw.Onlyinverse(dev, queue, src, src2, s["n"])
-    else:
-        plan = getattr(fw, kind)(dev, queue, src, s["n"])
-    assert not set(tunables) - set(KEY_ORDER)
-    for key in KEY_ORDER:
-        if key in tunables:
-            plan.set(key, tunables[key])
-    took = {k: int(plan.get(k)) for k in want}
-    if took != want:
+    plan = fw.plan_of_kind(kind, dev, queue, src, src2, s["n"])
+    try:
+        plan.configure(tunables)
+        took = {k: int(plan.get(k)) for k in want}
+        if took != want:
+            raise GeometryDrift("%s/%s: the plan took %s, the scenario names %s" % (tag, kind, took, want))
+    except Exception:
         plan.destroy()
-        raise GeometryDrift("%s/%s: the plan took %s, the scenario names %s" % (tag, kind, took, want))
+        raise
     return plan
-
-
-def upload(dev, queue, x):
-    buf = dev.create_buffer(x.nbytes)
-    queue.write_buffer(buf, 0, x)          # no encoder: waits on the host
-    return buf
 
 
 def expected(oracle, tag, kind, x, transforms):
@@ -118,8 +109,7 @@ def dft_failures(oracle, tag, kind, x, y, transforms, what):
     n = SHAPES[tag]["n"]
     bad = []
     for t, r in expected(oracle, tag, kind, x, transforms).items():
-        mx, l2 = oracle.compare(y[t * n:(t + 1) * n], r)
-        if not (mx <= REL_TOL and l2 <= REL_TOL):
+        for _, mx, l2 in parity_failures(y[t * n:(t + 1) * n], r, n, REL_TOL)[0]:
             bad.append("%s: transform %d against the fp64 DFT: max_rel %.3g rel_l2 %.3g (bound %g)" % (what, t, mx, l2, REL_TOL))
     return bad
 
@@ -194,26 +184,6 @@ class Pinned:
         self.dev.poll()
         while len(getattr(self.dev, "_pinned", [])) > self.mark:
             self.dev._L.fwa_host_free(self.dev._h, self.dev._pinned.pop())
-
-
-def hip_runtime():
-    """The HIP runtime image this process already runs (found in /proc/self/maps: no second runtime is loaded), with the
-    signatures of the few calls the graph scenarios make themselves."""
-    with open("/proc/self/maps") as f:
-        paths = [line.split()[-1] for line in f if "libamdhip64" in line]
-    if not paths:
-        return None
-    hip = ctypes.CDLL(paths[0])
-    P, PP = ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)
-    for name, args in (("hipStreamCreateWithFlags", [PP, ctypes.c_uint]), ("hipStreamDestroy", [P]),
-                       ("hipStreamBeginCapture", [P, ctypes.c_int]), ("hipStreamEndCapture", [P, PP]),
-                       ("hipGraphInstantiate", [PP, P, P, P, ctypes.c_size_t]), ("hipGraphLaunch", [P, P]),
-                       ("hipGraphGetNodes", [P, PP, ctypes.POINTER(ctypes.c_size_t)]),
-                       ("hipGraphNodeGetType", [P, ctypes.POINTER(ctypes.c_int)]),
-                       ("hipGraphExecDestroy", [P]), ("hipGraphDestroy", [P])):
-        fn = getattr(hip, name)
-        fn.argtypes, fn.restype = args, ctypes.c_int
-    return hip
 
 
 def hip_stream(hip):

@@ -252,7 +252,7 @@ void fwo_compare(const fwo_c32 *y, const fwo_c64 *r, uint32_t n,
         double dr = (double)y[k].re - r[k].re, di = (double)y[k].im - r[k].im;
         double d = sqrt(dr * dr + di * di);
         double m = sqrt(r[k].re * r[k].re + r[k].im * r[k].im);
-        if (!(d <= maxd)) maxd = d;   /* NaN-propagating max */
+        if (d > maxd || d != d) maxd = d;   /* NaN-propagating max: once NaN, maxd stays NaN */
         if (m > maxr) maxr = m;
         sd += d * d; sr += m * m;
     }

@@ -22,7 +22,7 @@ meets every condition on these inputs; tests/test_special_values.py is the stand
 
 Rows: the non-tiled rows of error_budget._CASES named in NON_TILED, and one tiled row per distinct smallest shape of
 kernel_cells.all_cells(), built as error_budget._cell_row builds its rows ("factors" and all four flag keys set by the row,
-every key read back by error_budget.run_case), so the kernel of every pass does not depend on the batch.  Every row runs
+every key read back by device_run.run), so the kernel of every pass does not depend on the batch.  Every row runs
 in Forward, Inverse and Onlyinverse.
 
 Batch layout: transforms alternate clean / special, so every special transform has clean neighbours on both sides.
@@ -56,6 +56,7 @@ import numpy as np
 
 from . import error_budget as eb
 from . import kernel_cells as kc
+from .device_run import run
 
 KINDS = eb.KINDS
 SCALES = (-40, 40, 90)
@@ -149,7 +150,7 @@ def ragged_case(case):
 
 
 ROWS = _rows()
-# every row in each of the three transforming plan kinds; id "<row>/<kind>".  The dicts carry what error_budget.run_case
+# every row in each of the three transforming plan kinds; id "<row>/<kind>".  The dicts carry what device_run.run
 # and kernel_cells.cells_of_case read.
 MATRIX = [dict(r, id="%s/%s" % (r["case"], kind), kind=kind, direction=direction) for r in ROWS for kind, direction in KINDS]
 
@@ -334,21 +335,24 @@ def check_results(layout, y_clean, y_poison, y_scaled):
 
 
 def run_row_kind(fw, dev, queue, oracle, case):
-    """The five execs of one case of MATRIX through the C ABI (error_budget.run_case), then the clean and the poisoned exec
+    """The five execs of one case of MATRIX through the C ABI (device_run.run), then the clean and the poisoned exec
     of its ragged layout -> (messages, plan facts, plan facts of the ragged layout)."""
+    def one(c, x):
+        y, _, facts = run(fw, dev, queue, c["kind"], x, c["n"], c["tunables"])
+        return y, facts
     layout = case["layout"]
     x = clean_input(oracle, layout)
-    y_clean, facts = eb.run_case(fw, dev, queue, case, x)
-    y_poison, facts_p = eb.run_case(fw, dev, queue, case, poisoned_input(x, layout))
+    y_clean, facts = one(case, x)
+    y_poison, facts_p = one(case, poisoned_input(x, layout))
     xs = scaling_input(x, layout)
-    y_scaled = {s: eb.run_case(fw, dev, queue, case, scaled(xs, s))[0] for s in SCALES}
+    y_scaled = {s: one(case, scaled(xs, s))[0] for s in SCALES}
     bad = ["%s: %s" % (case["id"], m) for m in check_results(layout, y_clean, y_poison, y_scaled)]
     if facts_p != facts:
         bad.append("%s: plan facts differ between the clean and the poisoned exec: %s / %s" % (case["id"], facts, facts_p))
     rc = ragged_case(case)
     x = clean_input(oracle, rc["layout"])
-    y_clean, facts_r = eb.run_case(fw, dev, queue, rc, x)
-    y_poison, facts_p = eb.run_case(fw, dev, queue, rc, poisoned_input(x, rc["layout"]))
+    y_clean, facts_r = one(rc, x)
+    y_poison, facts_p = one(rc, poisoned_input(x, rc["layout"]))
     bad += ["%s: %s" % (rc["id"], m) for m in check_poison(y_poison, y_clean, rc["layout"])]
     if facts_p != facts_r:
         bad.append("%s: plan facts differ between the clean and the poisoned exec: %s / %s" % (rc["id"], facts_r, facts_p))
@@ -357,20 +361,11 @@ def run_row_kind(fw, dev, queue, oracle, case):
 
 def run_normalize(fw, dev, queue, oracle, n, batch):
     """Normalize on normalize_input and at the three scales -> messages."""
+    even = (n.bit_length() - 1) % 2 == 0                      # processor.rs:433-439: reads buffer1 if log2 n is even
+
     def one(x):
-        a, b = dev.create_buffer(x.nbytes), dev.create_buffer(x.nbytes)
-        src = a if (n.bit_length() - 1) % 2 == 0 else b       # processor.rs:433-439: reads buffer1 if log2 n is even
-        queue.write_buffer(src, 0, x)
-        plan = fw.Normalize(dev, queue, a, b, n)
-        enc = dev.create_command_encoder()
-        out = plan.proc(enc)
-        queue.submit(enc.finish())
-        y = out.map_read(stream=enc)
-        ok = out is (b if src is a else a)
-        plan.destroy()
-        a.destroy()
-        b.destroy()
-        return y, ok
+        y, where, _ = run(fw, dev, queue, "Normalize", x, n, fill=lambda a, b: queue.write_buffer(a if even else b, 0, x))
+        return y, where == ("src2" if even else "src")
     x = normalize_input(oracle, n, batch)
     y, ok = one(x)
     bad = check_normalize(y, x, oracle.normalize_ref(x, n))

@@ -27,8 +27,8 @@ import pytest
 
 import guarded_arena as ga
 from conftest import REL_TOL
-from fft_wgpu_amd.processor import PLAN_KEYS
 from oracle import error_budget as eb
+from oracle.device_run import FACTS, facts_of, open_gpu, parity_failures, run
 
 pytestmark = pytest.mark.gpu
 
@@ -94,49 +94,11 @@ def families_without_cases(cases=None, specs=None):
 
 @pytest.fixture(scope="module")
 def gpu():
-    import fft_wgpu_amd as fw
-    got = fw.prepare_gpu(0)
-    assert got is not None, "no MI355X visible: the HIP path cannot run (there is no CPU fallback)"
-    dev, queue = got
-    return fw, dev, queue
-
-
-def _make_plan(fw, dev, queue, kind, n, src, src2, tunables):
-    plan = (fw.Onlyinverse(dev, queue, src, src2, n) if kind == "Onlyinverse" else getattr(fw, kind)(dev, queue, src, n))
-    assert not set(tunables) - set(PLAN_KEYS)
-    for key in PLAN_KEYS:                  # "factors" before "group": it resets it
-        if key in tunables:
-            plan.set(key, tunables[key])
-    return plan
-
-
-def _exec(fw, dev, queue, kind, n, src, src2, tunables):
-    """one exec -> (result, (path, factors, launches_per_exec), the buffer that holds the result)"""
-    plan = _make_plan(fw, dev, queue, kind, n, src, src2, tunables)
-    enc = dev.create_command_encoder()
-    out = plan.proc(enc)
-    y = out.map_read(stream=enc)
-    facts = tuple(int(plan.get(k)) for k in ("path", "factors", "launches_per_exec"))
-    where = "src" if out is src else ("src2" if out is src2 else "plan")
-    plan.destroy()
-    enc.destroy()
-    return y, facts, where
-
-
-def _on_base(fw, dev, queue, kind, n, x, tunables):
-    """the way the parity tests run a plan: fresh buffers at an allocation base"""
-    src = dev.create_buffer(x.nbytes)
-    queue.write_buffer(src, 0, x)
-    src2 = dev.create_buffer(x.nbytes) if kind == "Onlyinverse" else None
-    y, facts, where = _exec(fw, dev, queue, kind, n, src, src2, tunables)
-    for b in (src, src2):
-        if b is not None:
-            b.destroy()
-    return y, facts, where
+    return open_gpu()
 
 
 def _in_arena(fw, dev, queue, kind, n, x, tunables, extra, arena=None, start=None):
-    """the same on views inside a guarded arena -> (result, facts, where, guard reports)"""
+    """device_run.run on views inside a guarded arena -> (result, where, facts, guard reports)"""
     G = ga.guard_bytes(n)
     sizes = [x.nbytes, x.nbytes] if kind == "Onlyinverse" else [x.nbytes]
     own = arena is None
@@ -146,15 +108,14 @@ def _in_arena(fw, dev, queue, kind, n, x, tunables, extra, arena=None, start=Non
     views = arena.layout(sizes, start, names=["src", "src2"][:len(sizes)], whole=own)
     assert all(v.device_ptr % 16 == 0 and v.device_ptr != arena.device_ptr for v in views)
     src, src2 = views[0], (views[1] if len(views) > 1 else None)
-    queue.write_buffer(src, 0, x)
-    y, facts, where = _exec(fw, dev, queue, kind, n, src, src2, tunables)
+    y, where, facts = run(fw, dev, queue, kind, x, n, tunables, buffers=(src, src2))
     reports = arena.check()
     for v in views:
         v.destroy()
     arena.views = []
     if own:
         arena.destroy()
-    return y, facts, where, reports
+    return y, where, facts, reports
 
 
 def _same_bits(a, b):
@@ -162,29 +123,21 @@ def _same_bits(a, b):
 
 
 def _dft_failures(y, r, n, tol=REL_TOL):
-    """per-transform max_k |y - r| / max_k |r| and rel-L2, vectorised; NaN fails"""
-    bad = []
-    rows = max(1, (1 << 22) // n)
-    y, r = y.reshape(-1, n), r.reshape(-1, n)
-    for t0 in range(0, y.shape[0], rows):
-        yb, rb = y[t0:t0 + rows].astype(np.complex128), r[t0:t0 + rows]
-        d, m = np.abs(yb - rb), np.abs(rb)
-        ok = (d.max(axis=1) <= tol * m.max(axis=1)) & (np.sqrt((d * d).sum(axis=1)) <= tol * np.sqrt((m * m).sum(axis=1)))
-        bad += [t0 + int(i) for i in np.flatnonzero(~ok)[:4]]
-    return bad
+    """the first transforms that miss the parity rule; NaN fails"""
+    return [t for t, _, _ in parity_failures(y, r, n, tol)[0][:8]]
 
 
 def _run_spec(gpu, oracle, spec, runs=None, arena=None, start_of=None):
     """Assertions (a) - (c) for every (kind, start extra) of the spec; the input and its two fp64 DFTs are computed once."""
     fw, dev, queue = gpu
     n, batch, tun = spec["n"], spec["batch"], spec["tunables"]
-    want = (spec["path"], spec["factors"], spec["launches"])
+    want = dict(zip(FACTS, (spec["path"], spec["factors"], spec["launches"])))
     x = oracle.gen_input(n, batch, first_transform=3)
     dft = {}
     bad = []
     for kind, extras in (spec["runs"] if runs is None else runs):
         tag = "%s/%s" % (spec["id"], kind)
-        base, facts, base_where = _on_base(fw, dev, queue, kind, n, x, tun)
+        base, base_where, facts = run(fw, dev, queue, kind, x, n, tun)   # as the parity tests: fresh buffers at an allocation base
         if facts != want:
             bad.append("%s: plan took path/factors/launches %s, the case names %s" % (tag, facts, want))
         d = DIRECTION[kind]
@@ -195,7 +148,7 @@ def _run_spec(gpu, oracle, spec, runs=None, arena=None, start_of=None):
             bad.append("%s: base-buffer result misses the fp64 DFT at transforms %s" % (tag, off[:8]))
         for extra in extras:
             st = None if start_of is None else start_of(kind, extra)
-            y, facts, where, reports = _in_arena(fw, dev, queue, kind, n, x, tun, extra, arena, st)
+            y, where, facts, reports = _in_arena(fw, dev, queue, kind, n, x, tun, extra, arena, st)
             at = "%s @ %s" % (tag, "G + %d" % extra if start_of is None else "boundary in view %d" % extra)
             bad += ["%s: %s" % (at, m) for m in reports]                                      # (a)
             if not _same_bits(y, base):                                                       # (b)
@@ -357,7 +310,7 @@ def test_three_execs_back_to_back_on_poisoned_destinations(gpu, oracle, kind, n,
     (identical-looking) result shows here and nowhere else."""
     fw, dev, queue = gpu
     xs = [oracle.gen_input(n, batch, first_transform=100 * i) for i in range(3)]
-    singles = [_on_base(fw, dev, queue, kind, n, x, tunables)[0] for x in xs]
+    singles = [run(fw, dev, queue, kind, x, n, tunables)[0] for x in xs]
     bad = _dft_failures(singles[0], oracle.dft_f64(xs[0], n, DIRECTION[kind]), n)
     assert not bad, bad
     G = ga.guard_bytes(n)
@@ -366,8 +319,9 @@ def test_three_execs_back_to_back_on_poisoned_destinations(gpu, oracle, kind, n,
     arena = ga.GuardedArena(dev, queue, ga.arena_bytes(sizes, G + 16, G), G)
     views = arena.layout(sizes, G + 16, names=["src", "src2"][:len(sizes)])
     src, src2 = views[0], (views[1] if len(views) > 1 else None)
-    plan = _make_plan(fw, dev, queue, kind, n, src, src2, tunables)
-    assert tuple(int(plan.get(k)) for k in ("path", "factors", "launches_per_exec")) == want
+    plan = fw.plan_of_kind(kind, dev, queue, src, src2, n)
+    plan.configure(tunables)
+    assert facts_of(plan) == dict(zip(FACTS, want))
     dest = 1 if (kind == "Onlyinverse" and (n.bit_length() - 1) % 2) else 0
     keep = [dev.create_buffer(nbytes) for _ in xs]
     # page-locked staging: the uploads are truly asynchronous, nothing between two execs waits on the host

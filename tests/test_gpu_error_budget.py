@@ -13,6 +13,7 @@ import os
 import pytest
 
 from oracle import error_budget as eb
+from oracle.device_run import open_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -21,11 +22,7 @@ ROWS = sorted({c["case"] for c in eb.MATRIX}, key=[c["case"] for c in eb.MATRIX]
 
 @pytest.fixture(scope="module")
 def measured():
-    import fft_wgpu_amd as fw
-    got = fw.prepare_gpu(0)
-    assert got is not None, "no MI355X visible: the HIP path cannot run (there is no CPU fallback)"
-    dev, queue = got
-    return eb.measure(fw, dev, queue)
+    return eb.measure(*open_gpu())
 
 
 @pytest.fixture(scope="module")

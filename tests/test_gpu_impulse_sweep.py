@@ -16,17 +16,14 @@ import os
 import pytest
 
 from oracle import impulse_sweep as im
+from oracle.device_run import open_gpu
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def gpu():
-    import fft_wgpu_amd as fw
-    got = fw.prepare_gpu(0)
-    assert got is not None, "no MI355X visible: the HIP path cannot run (there is no CPU fallback)"
-    dev, queue = got
-    return fw, dev, queue
+    return open_gpu()
 
 
 @pytest.fixture(scope="module")

@@ -12,17 +12,15 @@ import numpy as np
 import pytest
 
 from conftest import REL_TOL  # noqa: F401
-from test_gpu_parity import _check, _fixture_sizes_body, _run, _upload
+from oracle.device_run import open_gpu, upload
+from parity_cases import check as _check, fixture_sizes_body, run as _run
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def gpu():
-    import fft_wgpu_amd as fw
-    got = fw.prepare_gpu(0, lab=True)
-    assert got is not None, "no MI355X visible: the HIP path cannot run (there is no CPU fallback)"
-    dev, queue = got
+    fw, dev, queue = open_gpu(lab=True)
     assert dev.lab
     return fw, dev, queue
 
@@ -31,7 +29,7 @@ def gpu():
 def test_fixture_sizes_laboratory_kernels(gpu, oracle, k4, small_reg):
     """the 16-point kernels at 16 .. 4096 (small_reg = 3; the shipped kernels below and above), + the wavefront-shuffle
     exchange at n = 32 / 64 / 128 (2): every fixture size, forward / unscaled inverse / inverse."""
-    _fixture_sizes_body(gpu, oracle, k4, None, small_reg)
+    fixture_sizes_body(gpu, k4, None, small_reg)
 
 
 def test_small_reg_accepts_only_its_three_values(gpu):
@@ -52,12 +50,12 @@ def test_n1m_ring_rotate_is_bit_identical(gpu, oracle):
     fw, dev, queue = gpu
     n, batch = 1 << 20, 40
     x = oracle.gen_input(n, batch, first_transform=9)
-    ref, _, plan0 = _run(fw, dev, queue, "Forward", x, n, group=4, streams=2)
+    ref, _, facts0 = _run(fw, dev, queue, "Forward", x, n, group=4, streams=2)
     mx, _ = oracle.compare(ref[:n], oracle.dft_f64(x[:n], n, -1))
     assert mx <= REL_TOL
     for rot in (2, 5):
-        y, _, plan = _run(fw, dev, queue, "Forward", x, n, group=4, streams=2, ring_rotate=rot)
-        assert plan.get("ring_rotate") == rot and plan.get("scratch_bytes") == rot * plan0.get("scratch_bytes")
+        y, _, facts = _run(fw, dev, queue, "Forward", x, n, group=4, streams=2, ring_rotate=rot)
+        assert facts["ring_rotate"] == rot and facts["scratch_bytes"] == rot * facts0["scratch_bytes"]
         assert np.array_equal(y.view(np.uint64), ref.view(np.uint64))
 
 
@@ -70,16 +68,16 @@ def test_n1m_persistent_ring_pipeline(gpu, oracle, batch, depth, slots, wgs):
     n = 1 << 20
     x = oracle.gen_input(n, batch, first_transform=batch)
     ref, _, _ = _run(fw, dev, queue, "Forward", x, n, path=1, tile_w=16)
-    _check(oracle, ref, oracle.dft_f64(x, n, -1), n)
+    _check(ref, oracle.dft_f64(x, n, -1), n)
     for rep in range(2):
-        y, which, plan = _run(fw, dev, queue, "Forward", x, n, path=5, depth=depth, ring_slots=slots, wgs=wgs)
-        assert which == 0 and plan.get("path") == 5 and plan.get("launches_per_exec") == 1
-        assert plan.get("device_error") == 0
+        y, which, facts = _run(fw, dev, queue, "Forward", x, n, path=5, depth=depth, ring_slots=slots, wgs=wgs)
+        assert which == 0 and facts["path"] == 5 and facts["launches_per_exec"] == 1
+        assert facts["device_error"] == 0
         bad = np.flatnonzero(y.view(np.uint64) != ref.view(np.uint64))
         assert bad.size == 0, (batch, depth, slots, wgs, rep, bad.size, bad[:8])
-    z, _, plan = _run(fw, dev, queue, "Inverse", ref, n, path=5, depth=depth, ring_slots=slots, wgs=wgs)
-    assert plan.get("device_error") == 0
-    _check(oracle, z, x.astype(np.complex128), n)
+    z, _, facts = _run(fw, dev, queue, "Inverse", ref, n, path=5, depth=depth, ring_slots=slots, wgs=wgs)
+    assert facts["device_error"] == 0
+    _check(z, x.astype(np.complex128), n)
 
 
 def test_n1m_persistent_ring_large_batch_bit_identical(gpu, oracle):
@@ -91,8 +89,8 @@ def test_n1m_persistent_ring_large_batch_bit_identical(gpu, oracle):
     ref, _, _ = _run(fw, dev, queue, "Forward", x, n, path=1)
     for kw in (dict(), dict(depth=4, ring_slots=6), dict(depth=8, ring_slots=12, wgs=256), dict(depth=2, ring_slots=3)):
         for rep in range(2):
-            y, _, plan = _run(fw, dev, queue, "Forward", x, n, path=5, **kw)
-            assert plan.get("device_error") == 0
+            y, _, facts = _run(fw, dev, queue, "Forward", x, n, path=5, **kw)
+            assert facts["device_error"] == 0
             bad = np.flatnonzero(y.view(np.uint64) != ref.view(np.uint64))
             assert bad.size == 0, (kw, rep, bad.size, bad[:8])
 
@@ -136,7 +134,7 @@ def test_path_round_trip_through_the_persistent_ring_leaves_a_plain_two_pass_pla
     n, batch = 1 << 20, 4
     x = oracle.gen_input(n, batch, first_transform=13)
     enc = dev.create_command_encoder()
-    bufs = [_upload(fw, dev, queue, x) for _ in range(2)]
+    bufs = [upload(dev, queue, x) for _ in range(2)]
     for path in (1, 5):     # the context has its 2^20 tables and both kernel families loaded before memory is measured
         warm = fw.Forward(dev, queue, bufs[0], n)
         assert warm.get("path") == 1
@@ -158,7 +156,7 @@ def test_path_round_trip_through_the_persistent_ring_leaves_a_plain_two_pass_pla
     assert fresh.get("path") == 1 and fresh.get("scratch_bytes") == batch * n * 8
     y_fresh, y_trip = (p.proc(enc).map_read(stream=enc) for p in (fresh, trip))
     assert np.array_equal(y_trip.view(np.uint64), y_fresh.view(np.uint64))
-    _check(oracle, y_fresh, oracle.dft_f64(x, n, -1), n)
+    _check(y_fresh, oracle.dft_f64(x, n, -1), n)
     fresh.destroy()
     trip.destroy()
     dev.poll()

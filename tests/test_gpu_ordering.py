@@ -12,17 +12,14 @@ ordering edge each (profiles/round7/ordering_mutants.jsonl).
 import pytest
 
 from oracle import ordering
+from oracle.device_run import open_gpu
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def gpu():
-    import fft_wgpu_amd as fw
-    got = fw.prepare_gpu(0)
-    assert got is not None, "no MI355X visible: the HIP path cannot run (there is no CPU fallback)"
-    dev, queue = got
-    return fw, dev, queue
+    return open_gpu()
 
 
 @pytest.mark.parametrize("scenario", [s for _, s in ordering.SCENARIOS], ids=[i for i, _ in ordering.SCENARIOS])

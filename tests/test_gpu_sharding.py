@@ -14,18 +14,15 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_gpu_parity import _hip_runtime, _run
+from oracle.device_run import open_gpu
+from parity_cases import hip_runtime, run as _run
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def gpu():
-    import fft_wgpu_amd as fw
-    got = fw.prepare_gpu(0)
-    assert got is not None, "no MI355X visible: the HIP path cannot run (there is no CPU fallback)"
-    dev, queue = got
-    return fw, dev, queue
+    return open_gpu()
 
 
 def test_enumerate_adapters_lists_every_ordinal(gpu):
@@ -240,7 +237,7 @@ def test_stream_overlap_check_is_refused_during_capture_and_can_be_turned_off(gp
     it runs only when there is a peer to overlap with, never while a stream of the context captures a graph
     (FWA_ERR_UNSUPPORTED), and fwa_ctx_set_i64("chain_check", 0) turns it off."""
     fw, _, _ = gpu
-    hip = _hip_runtime()
+    hip = hip_runtime()
     d = fw.Device(0)
     base = d.get("chain_checks")
     first = d.create_command_encoder()

@@ -1,6 +1,6 @@
 """GPU: NaN propagation, batch isolation and exact 2^s scaling of every kernel (oracle/special_values.py).
 
-One test per row, over its three plan kinds, through the C ABI with the call sequence of error_budget.run_case: the
+One test per row, over its three plan kinds, through the C ABI with the call sequence of device_run.run: the
 plan must take the path / factorisation / launch count the row names; then
   * one input sample NaN + NaN i makes all 2n output floats of its transform NaN, +Inf - Inf i leaves no output finite in
     both parts, an all-zero transform gives zero;
@@ -17,17 +17,14 @@ import numpy as np
 import pytest
 
 from oracle import special_values as sv
+from oracle.device_run import open_gpu
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def gpu():
-    import fft_wgpu_amd as fw
-    got = fw.prepare_gpu(0)
-    assert got is not None, "no MI355X visible: the HIP path cannot run (there is no CPU fallback)"
-    dev, queue = got
-    return fw, dev, queue
+    return open_gpu()
 
 
 @pytest.mark.parametrize("row", [r["case"] for r in sv.ROWS])

@@ -9,7 +9,6 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fft_wgpu_amd as fw  # noqa: E402
-from fft_wgpu_amd.processor import PLAN_KEYS  # noqa: E402
 from sweep import parse_setting  # noqa: E402
 
 
@@ -25,17 +24,11 @@ def main():
     dev, queue = fw.prepare_gpu(0, lab=args.lab)
     n = 1 << args.lg
     enc = dev.create_command_encoder()
-    if args.kind == "normalize":       # normalize.wgsl:9-12: buffer1 -> buffer2, 16 B per sample like a transform
-        buf = dev.create_buffer(n * args.batch * 8)
-        second = dev.create_buffer(n * args.batch * 8)
-        plan = fw.Normalize(dev, queue, buf, second, n)
-    else:
-        buf = dev.create_buffer(n * args.batch * 8)
-        plan = fw.Forward(dev, queue, buf, n)
-    kv = parse_setting(args.set)
-    for key in PLAN_KEYS:
-        if key in kv:
-            plan.set(key, kv[key])
+    buf = dev.create_buffer(n * args.batch * 8)
+    # normalize.wgsl:9-12: buffer1 -> buffer2, 16 B per sample like a transform
+    second = dev.create_buffer(n * args.batch * 8) if args.kind == "normalize" else None
+    plan = fw.plan_of_kind(args.kind.capitalize(), dev, queue, buf, second, n)
+    plan.configure(parse_setting(args.set), verify=False)      # a clamped key shows in the printed line
     ms = []
     for _ in range(args.execs):
         dev.fill_synthetic(buf, n, scale=2.0 ** -40, encoder=enc)

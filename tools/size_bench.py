@@ -34,8 +34,7 @@ def main():
         n = 1 << lg
         view = dev.wrap_buffer(buf.device_ptr, n * batch * 8)
         plan = fw.Forward(dev, queue, view, n)
-        for key, val in kv.items():
-            plan.set(key, val)
+        plan.configure(kv, verify=False)
         reps = 5 if n * batch >= (1 << 31) else (15 if n * batch >= (1 << 24) else 50)
         times = []
         # Warm-up: at least one exec and at least WARM_MS of them.  For some tens of milliseconds after a multi-GiB hipMalloc /

@@ -15,7 +15,6 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fft_wgpu_amd as fw  # noqa: E402
-from fft_wgpu_amd.processor import PLAN_KEYS  # noqa: E402
 
 
 def parse_setting(s):
@@ -69,10 +68,7 @@ def main():
     plans = []
     for s in settings:
         plan = fw.Forward(dev, queue, buf, n)
-        kv = parse_setting(s)
-        for key in PLAN_KEYS:
-            if key in kv:
-                plan.set(key, kv[key])
+        plan.configure(parse_setting(s), verify=False)         # the JSON line reports what the plan holds
         plans.append((s, plan, []))
     # one regeneration of the input per round: log2(n) <= 30 bits of growth per exec, 2^-40 input scale and at most
     # 3 execs between refills keep fp32 finite

@@ -11,7 +11,7 @@ for batch, kw in ((5, {}), (21, {"group": 4, "streams": 2})):
     x = oracle.gen_input(n, batch, first_transform=7)
     src = dev.create_buffer(x.nbytes); queue.write_buffer(src, 0, x)
     plan = fw.Forward(dev, queue, src, n)
-    for k, v in kw.items(): plan.set(k, v)
+    plan.configure(kw)
     assert plan.get("path") == 1
     y = plan.proc(enc).map_read(stream=enc)
     r = oracle.dft_f64(x[:2 * n], n, -1)
