@@ -43,9 +43,13 @@ from _cell_row are the cells the hand-picked rows left out, each at the smallest
 reaches it; they set "factors" and all four flags themselves, and device_run.run reads every key back.
 
 Out of the matrix on purpose: the 2^27..2^30 impulse test (tests/test_gpu_parity.py) keeps the flat bound; at those
-sizes a one-index twiddle error rotates by 2 pi / N <= 5e-8, below fp32 resolution.  With it stays what only a
-transform of >= 4 GiB (n >= 2^29) tells apart: the 64-bit-pointer form of k_tile (a tile spanning 2^32 bytes) and the four
-buffer descriptors of k_p1_gen, one per quarter of a transform, which below that size address what a single one would.
+sizes a one-index twiddle error rotates by 2 pi / N <= 5e-8, below fp32 resolution, and a dense fp64 reference costs O(n)
+host work per output.  What only a transform of >= 4 GiB (n >= 2^29) tells apart -- the 64-bit-pointer form of k_tile (a
+tile spanning 2^32 bytes) and the four buffer descriptors of k_p1_gen, one per quarter of a transform, which below that
+size address what a single one would -- and the 2^19 .. 2^20-entry hi[] tables of those sizes are held by
+oracle/large_plans.py instead: sparse inputs (swept impulses and combs) through every accepted factorisation of 2^29 and
+2^30 in every plan kind, each compared output within pi / 2^20 of an exact float64 reference, the combs within this flat
+bound.
 """
 import hashlib
 import json

@@ -22,7 +22,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "tiled_schedule.txt")
 
 # the lengths whose decisions can differ by kernel form: below 2^16 there is no tiled plan, above 2^28 the 32-bit-offset
-# kernels (colsw, cols32, rows32) leave and only k_tile / k_p1_gen remain, in forms that 2^16 .. 2^28 have already
+# kernels (colsw, cols32, rows32) leave and only k_tile / k_p1_gen remain.  The decisions there name no new cell, but the code
+# is not all met below: from 2^29 pass A as k_tile columns and the last pass as k_tile rows run in the 64-bit-pointer form
+# (launch_tile: a tile spanning 2^32 bytes) and the four buffer descriptors of k_p1_gen address what one no longer could.
+# Those forms, one row per accepted factor tuple of 2^29 and 2^30, belong to oracle/large_plans.py, not to this matrix.
 LG_RANGE = range(16, 29)
 FLAG_KEYS = ("colsw", "rows32", "p1_gen", "tile_ring")   # bit 0 .. 3 of a flag index, as schedule.h flag_setting
 PATH_TILED = 7

@@ -12,6 +12,7 @@ from fft_wgpu_amd.processor import PLAN_KEYS, _Plan
 from oracle import device_run as dr
 from oracle import error_budget as eb
 from oracle import impulse_sweep as im
+from oracle import large_plans as lp
 from oracle import ordering
 from oracle import special_values as sv
 
@@ -92,6 +93,8 @@ def _matrices():
         yield "special_values " + case["id"] + "/ragged", sv.ragged_case(case)["tunables"], _factors_first
     for case in im.MATRIX:
         yield "impulse_sweep " + case["id"], case["tunables"], _factors_first
+    for case in lp.MATRIX:
+        yield "large_plans " + case["id"], case["tunables"], _plan_keys_order      # written for configure
     for tag, shape in ordering.SHAPES.items():
         yield "ordering " + tag, shape["tunables"], _ordering_order
     for spec in tc.build_specs():
