@@ -10,6 +10,7 @@ from .pipeline import HostPipeline  # noqa: F401
 from .processor import (PLAN_KEYS, SECOND_BUFFER_KINDS, Forward, Inverse, Normalize, Onlyinverse,  # noqa: F401
                         plan_of_kind)
 from .sharding import Comm, ShardedBatch, slab  # noqa: F401
+from . import strided  # noqa: F401  (column transforms of row-major matrices; its library loads on first use)
 
 COMPLEX_BYTES = 8  # src/lib.rs:10-15: {real: f32, imag: f32}
 
