@@ -19,32 +19,11 @@
 // with 32-bit offsets (BIG = false); larger ones through 64-bit pointers (BIG = true).  The matrix base is 64-bit in both.
 #include "../csrc/device_common.h"
 #include "strided_kernels.h"
+#include "strided_net.h"
 
 namespace fws {
 
 using namespace fwa;
-
-struct TwTable {
-    float v[4096];  // {re, im} of W_4096^k = exp(-2 pi i k / 4096), k < 2048
-};
-constexpr TwTable make_tw_table()
-{
-    TwTable t{};
-    for (int k = 0; k < 2048; ++k) {
-        t.v[2 * k] = (float)cx_cos2pi(k, 4096);
-        t.v[2 * k + 1] = (float)-cx_sin2pi(k, 4096);
-    }
-    return t;
-}
-__device__ const TwTable g_tw alignas(16) = make_tw_table();
-
-template <int N>
-__device__ __forceinline__ v2f tw_n(uint32_t e)  // W_N^e, 0 <= e < N
-{
-    const uint32_t i = e * (4096 / N);
-    const v2f w = reinterpret_cast<const v2f *>(g_tw.v)[i & 2047u];
-    return (i & 2048u) ? -w : w;
-}
 
 // The rows row0 + i * row_step of one column of one matrix.  The caller masks: a lane whose column does not exist calls
 // neither load nor store.
@@ -102,58 +81,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void k_strided_small(v2f *buf, uint6
 // ---------------------------------------------------------------------------
 // n >= 64: W columns per workgroup, P points per thread, two or three stages.
 // ---------------------------------------------------------------------------
-// Stage of radix R with sub-block size J on the P points of thread t.  Output q of butterfly g is left in x[g + q*P/R]; it
-// is element dest<..>(t, g) + q*J of the column (exchange below), or, after the last stage, element t + T*(g + q*P/R).
-template <int N, int P, int R, int J, int DIR>
-__device__ __forceinline__ void stage(v2f (&x)[P], uint32_t t)
-{
-    constexpr int G = P / R, T = N / P;
-    static_for<0, G>([&](auto g_) {
-        constexpr int g = decltype(g_)::value;
-        v2f v[R];
-        static_for<0, R>([&](auto m_) { constexpr int m = decltype(m_)::value; v[m] = x[g + m * G]; });
-        fft_reg<R, DIR>(v);
-        const uint32_t idx = t + T * g;
-        const uint32_t sJ = idx & ~(uint32_t)(J - 1);
-        static_for<0, R>([&](auto q_) {
-            constexpr int q = decltype(q_)::value;
-            v2f y = v[brev<R>(q)];
-            if constexpr (q != 0 && J * R < N) y = cmul_tw<DIR>(y, tw_n<N>(sJ * q));
-            x[g + q * G] = y;
-        });
-    });
-}
-
-// The points of a stage<N, P, R, J> go to the threads of the next stage: plane-wise, swizzled (file comment).
-template <int N, int P, int R, int J, int W, int LGR0, bool FIRST>
-__device__ __forceinline__ void exchange(v2f (&x)[P], float *xch, uint32_t t, uint32_t c)
-{
-    constexpr int G = P / R, T = N / P;
-    auto word = [&](uint32_t d) { return (d ^ ((d >> LGR0) & 3u)) * W + c; };
-    auto dest = [&](int g, int q) {
-        const uint32_t idx = t + T * g, j = idx & (uint32_t)(J - 1);
-        return (idx - j) * R + j + q * J;
-    };
-    if constexpr (!FIRST) __syncthreads();  // the reads of the exchange before this one
-    static_for<0, G>([&](auto g_) {
-        static_for<0, R>([&](auto q_) {
-            constexpr int g = decltype(g_)::value, q = decltype(q_)::value;
-            xch[word(dest(g, q))] = x[g + q * G].x;
-        });
-    });
-    __syncthreads();
-    static_for<0, P>([&](auto m_) { constexpr int m = decltype(m_)::value; x[m].x = xch[word(t + T * m)]; });
-    __syncthreads();
-    static_for<0, G>([&](auto g_) {
-        static_for<0, R>([&](auto q_) {
-            constexpr int g = decltype(g_)::value, q = decltype(q_)::value;
-            xch[word(dest(g, q))] = x[g + q * G].y;
-        });
-    });
-    __syncthreads();
-    static_for<0, P>([&](auto m_) { constexpr int m = decltype(m_)::value; x[m].y = xch[word(t + T * m)]; });
-}
-
+// (the stages and the exchange between them: strided_net.h)
 template <int LGN, int DIR, bool BIG>
 __global__ __launch_bounds__(geometry(1u << LGN).threads) void k_strided(v2f *buf, uint64_t howmany, uint32_t tiles,
                                                                          float scale, uint32_t xcd_swizzle)
@@ -179,10 +107,11 @@ __global__ __launch_bounds__(geometry(1u << LGN).threads) void k_strided(v2f *bu
     if (live) static_for<0, P>([&](auto m_) { constexpr int m = decltype(m_)::value; x[m] = rows.load(m); });
 
     stage<N, P, K.r0, 1, DIR>(x, t);
-    exchange<N, P, K.r0, 1, W, LGR0, true>(x, xch, t, c);
+    auto word = [c](uint32_t d) { return (d ^ ((d >> LGR0) & 3u)) * W + c; };
+    exchange<N, P, K.r0, 1, true>(x, xch, t, word);
     stage<N, P, K.r1, K.r0, DIR>(x, t);
     if constexpr (K.r2 > 1) {
-        exchange<N, P, K.r1, K.r0, W, LGR0, false>(x, xch, t, c);
+        exchange<N, P, K.r1, K.r0, false>(x, xch, t, word);
         stage<N, P, K.r2, K.r0 * K.r1, DIR>(x, t);
     }
 
