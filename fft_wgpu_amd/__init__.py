@@ -12,6 +12,7 @@ from .processor import (PLAN_KEYS, SECOND_BUFFER_KINDS, Forward, Inverse, Normal
 from .sharding import Comm, ShardedBatch, slab  # noqa: F401
 from . import strided  # noqa: F401  (column transforms of row-major matrices; its library loads on first use)
 from . import fft2d  # noqa: F401  (in-place 2-D transforms of batched row-major images; likewise)
+from . import real  # noqa: F401  (rfft / irfft of batched real rows, out of place; likewise)
 
 COMPLEX_BYTES = 8  # src/lib.rs:10-15: {real: f32, imag: f32}
 
