@@ -19,7 +19,8 @@ from oracle import error_budget as eb
 LENGTHS = [1 << lg for lg in range(1, 13)]
 SHAPES = [2, 32, 64, 512, 1024, 2048, 4096]          # one butterfly; last chunk-shape length; first network (8 x 8); 32-point
 #                                                      stages (512, 1024); three stages (2048); RT = 8 (4096)
-ONEHOT_LENGTHS = [2, 32, 64, 1024, 2048, 4096]
+ONEHOT_LENGTHS = LENGTHS                             # the one-hot sweep runs at every length ...
+ONEHOT_CONJ = (False, True)                          # ... through both conj_filter forms of the kernel (a one-hot 1 + 0i is its own conjugate)
 KINDS = ("Convolve", "OnlyConvolve")
 ONEHOT_ANGLE, ONEHOT_MODULUS = 2 * np.pi / 2 ** 20, 2e-6
 

@@ -2,8 +2,10 @@
 
 The inputs, the float64 reference and every numeric bound live in tests/conv_cases.py, which tests/test_conv.py also applies
 to a numpy complex64 model on the CPU: parity (per row, REL_TOL), the cap (whole-buffer rel-L2 <= cap(2 n n)), the one-hot
-sweep (2 pi / 2^20 in angle, 2e-6 in modulus relative to 1 / n) and the shifts.  Everything else here is bit for bit.  With
-CONV_RECORD=<path> in the environment the cap test also writes the measured figures there (tests/golden/conv_error.json is
+sweep (2 pi / 2^20 in angle, 2e-6 in modulus relative to 1 / n; at every n, through both conj_filter forms) and the shifts;
+test_budget_per_class holds every class of tests/side_sweeps.py's maps (line mod RT or the owning thread of a chunk, element
+mod T and div T) to the same cap, on the execs test_error_cap made.  Everything else here is bit for bit.  With
+CONV_RECORD=<path> in the environment the cap tests also write the measured figures there (tests/golden/conv_error.json is
 such a record; no test pins to it).
 
 Shapes: n = 2 (one butterfly), 32 (the last chunk-shape length), 64 (the first network, 8 x 8), 512 and 1024 (32-point
@@ -21,6 +23,7 @@ import torch  # before the library: one HIP runtime in the process, the one torc
 
 import conv_cases as cc
 import guarded_arena as ga
+import side_sweeps as ss
 from oracle.device_run import open_gpu
 
 pytestmark = pytest.mark.gpu
@@ -110,36 +113,62 @@ def test_one_filter_and_one_filter_per_row(conv, gpu, oracle, n):
 
 # ---- error cap ------------------------------------------------------------------------------------------------------
 _measured = {}
+_cap_runs = {}
+
+
+def cap_run(conv, gpu, oracle, n):
+    """The two execs (conj_filter off and on) of one length at >= 2^18 samples, shared by the two cap tests: (failures of
+    the whole-buffer cap, failures of the per-class check)."""
+    if n not in _cap_runs:
+        batch = cc.cap_batch(n)
+        x, H = cc.inputs(oracle, n, batch, 3)[0], cc.cap_filters(oracle, n)
+        bad, class_bad = [], []
+        for conj in (False, True):
+            ref = cc.reference(x, H, "Convolve", conj)
+            y = run(conv, gpu, "Convolve", x, H, n, conj)
+            what = "n %d conj %d batch %d" % (n, conj, batch)
+            bad += cc.cap_failures(y, ref, n, what)
+            mx, _ = cc.row_errors(oracle, y, ref)
+            more, spread = ss.class_failures(y, ref, ss.lines_classes(n, batch), cc.cap(n), "conv " + what)
+            class_bad += more
+            _measured["%d/%s" % (n, "conj" if conj else "plain")] = dict(
+                {"n": n, "conj_filter": conj, "batch": batch, "rel_l2": cc.whole_rel_l2(y, ref), "max_rel": mx, "cap": cc.cap(n)},
+                **ss.spread_record(spread))
+        path = os.environ.get("CONV_RECORD")
+        if path:
+            with open(path, "w") as f:
+                json.dump({"metric": "whole-buffer rel-L2 (and worst per-row max_rel) against numpy.fft.ifft(numpy.fft.fft(x) * H) in float64, "
+                                     "scaled kind, three filters; per class (tests/side_sweeps.py) as a fraction of the cap",
+                           "cases": _measured}, f, indent=1, sort_keys=True)
+        _cap_runs[n] = (bad, class_bad)
+    return _cap_runs[n]
 
 
 @pytest.mark.parametrize("n", cc.LENGTHS)
 def test_error_cap(conv, gpu, oracle, n):
     """>= 2^18 samples per length, three filters (flat random, a decaying impulse response, a 60-dB low-pass): whole-buffer
     rel-L2 under cap(2 n n)"""
-    batch = cc.cap_batch(n)
-    x, H = cc.inputs(oracle, n, batch, 3)[0], cc.cap_filters(oracle, n)
-    bad = []
-    for conj in (False, True):
-        ref = cc.reference(x, H, "Convolve", conj)
-        y = run(conv, gpu, "Convolve", x, H, n, conj)
-        bad += cc.cap_failures(y, ref, n, "n %d conj %d batch %d" % (n, conj, batch))
-        mx, _ = cc.row_errors(oracle, y, ref)
-        _measured["%d/%s" % (n, "conj" if conj else "plain")] = {"n": n, "conj_filter": conj, "batch": batch, "rel_l2": cc.whole_rel_l2(y, ref),
-                                                               "max_rel": mx, "cap": cc.cap(n)}
-    path = os.environ.get("CONV_RECORD")
-    if path:
-        with open(path, "w") as f:
-            json.dump({"metric": "whole-buffer rel-L2 (and worst per-row max_rel) against numpy.fft.ifft(numpy.fft.fft(x) * H) in float64, "
-                                 "scaled kind, three filters", "cases": _measured}, f, indent=1, sort_keys=True)
+    bad, _ = cap_run(conv, gpu, oracle, n)
+    assert not bad, "\n".join(bad)
+
+
+@pytest.mark.parametrize("n", cc.LENGTHS)
+def test_budget_per_class(conv, gpu, oracle, n):
+    """the same execs: every class of rows (the lane group of a tile, the thread of a chunk) and of elements (thread and
+    register of the network) under the same cap"""
+    _, bad = cap_run(conv, gpu, oracle, n)
     assert not bad, "\n".join(bad)
 
 
 # ---- every bin meets its own filter sample ----------------------------------------------------------------------------
 @pytest.mark.parametrize("n", cc.ONEHOT_LENGTHS)
 def test_every_bin_meets_its_own_filter_sample(conv, gpu, n):
-    """batch = F = n, filter row b one-hot at bin b, src row b a unit impulse: row b answers with the tone of bin b"""
+    """batch = F = n, filter row b one-hot at bin b, src row b a unit impulse: row b answers with the tone of bin b, through
+    the plain and the conjugating form of the kernel (1 + 0i is its own conjugate: the same answer)"""
     x, H = cc.onehot_inputs(n)
-    bad = cc.onehot_failures(run(conv, gpu, "Convolve", x, H, n), n)
+    bad = []
+    for conj in cc.ONEHOT_CONJ:
+        bad += ["conj %d, %s" % (conj, m) for m in cc.onehot_failures(run(conv, gpu, "Convolve", x, H, n, conj), n)]
     assert not bad, "\n".join(bad)
 
 

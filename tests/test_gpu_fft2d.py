@@ -5,8 +5,13 @@ reshaped to (batch, rows, cols).  A reference is computed once per shape and sha
   parity       per image, oracle.compare's max_rel and rel-L2 <= REL_TOL (tests/conftest.py)
   budget       whole-buffer rel-L2 <= oracle.error_budget.cap(rows * cols): each pass is held under the cap of its own
                length, cap(n) = C 2^-24 sqrt(log2 n), and cap(cols)^2 + cap(rows)^2 = cap(rows * cols)^2
-  impulses     pi / 2^20 in angle and 1e-6 in modulus, the bound of the project's impulse sweeps
-Everything else is bit for bit.  With FFT2D_RECORD=<path> in the environment the budget test also writes the measured
+  per class    test_budget_per_class: the same cap on the rel-L2 of every class of tests/side_sweeps.py's maps (row pass:
+               line mod RT, element mod T and div T, or the owning thread of a chunk; column pass: those of the strided
+               plan, or the thread of the fused column phase), on the exec test_budget made
+  impulses     pi / 2^20 in angle and 1e-6 in modulus, the bound of the project's impulse sweeps; test_dft_matrix_sweep
+               (tests/side_sweeps.py) reads the full 2-D matrix out of all 25 fused pairs and one impulse per column
+               position out of the row kernels at every width, per output
+Everything else is bit for bit.  With FFT2D_RECORD=<path> in the environment the budget tests also write the measured
 figures there (tests/golden/fft2d_error.json is such a record; no test pins to it).
 """
 import ctypes
@@ -19,6 +24,7 @@ import pytest
 import torch  # before the library: one HIP runtime in the process, the one torch brings (as in bench.py)
 
 import guarded_arena as ga
+import side_sweeps as ss
 from conftest import REL_TOL
 from oracle import error_budget as eb
 from oracle.device_run import open_gpu
@@ -136,17 +142,17 @@ def test_parity_of_two_row_images(fft2d, gpu, oracle, cols, batch):
 _measured = {}
 
 
-def _budget(rows, cols, kind, batch, y, r):
+def _budget(rows, cols, kind, batch, y, r, spread=None):
     n = rows * cols
     rel_l2 = float(np.sqrt((np.abs(y - r) ** 2).sum() / (np.abs(r) ** 2).sum()))
     print("budget %d x %d %s batch %d: rel_l2 %.4g = %.3f of the cap %.4g" % (rows, cols, kind, batch, rel_l2, rel_l2 / eb.cap(n), eb.cap(n)))
-    _measured["%dx%d/%s" % (rows, cols, kind)] = {"rows": rows, "cols": cols, "kind": kind, "batch": batch, "rel_l2": rel_l2,
-                                                  "cap": float(eb.cap(n))}
+    _measured["%dx%d/%s" % (rows, cols, kind)] = dict({"rows": rows, "cols": cols, "kind": kind, "batch": batch, "rel_l2": rel_l2,
+                                                       "cap": float(eb.cap(n))}, **(ss.spread_record(spread) if spread else {}))
     path = os.environ.get("FFT2D_RECORD")
     if path:
         with open(path, "w") as f:
-            json.dump({"metric": "whole-buffer rel-L2 against numpy.fft.fft2 / ifft2 in float64", "cases": _measured}, f, indent=1,
-                      sort_keys=True)
+            json.dump({"metric": "whole-buffer rel-L2 against numpy.fft.fft2 / ifft2 in float64; per class (tests/side_sweeps.py) as "
+                                 "a fraction of the cap", "cases": _measured}, f, indent=1, sort_keys=True)
     return rel_l2
 
 
@@ -162,14 +168,48 @@ def test_parity_4096_x_4096(fft2d, gpu, oracle):
 
 
 # ---- budget ---------------------------------------------------------------------------------------------------------
+_budget_runs = {}
+
+
+def budget_run(fft2d, gpu, oracle, rows, cols, kind):
+    """One exec per (shape, kind) at >= 2^18 samples, shared by the two budget tests: (whole-buffer rel-L2, failures of the
+    per-class check)."""
+    key = (rows, cols, kind)
+    if key not in _budget_runs:
+        batch = -(-eb.MIN_SAMPLES // (rows * cols))
+        x, ref = images(oracle, rows, cols, batch)
+        y = run(fft2d, gpu, kind, x, rows, cols)
+        bad, spread = ss.class_failures(y, ref[kind], ss.fft2d_classes(rows, cols, batch), float(eb.cap(rows * cols)),
+                                        "fft2d %s %d x %d" % (kind, rows, cols))
+        _budget_runs[key] = (_budget(rows, cols, kind, batch, y, ref[kind], spread), bad)
+    return _budget_runs[key]
+
+
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("rows,cols", SHAPES)
 def test_budget(fft2d, gpu, oracle, rows, cols, kind):
     """>= 2^18 samples per shape: whole-buffer rel-L2 under the cap of rows * cols"""
-    batch = -(-eb.MIN_SAMPLES // (rows * cols))
-    x, ref = images(oracle, rows, cols, batch)
-    y = run(fft2d, gpu, kind, x, rows, cols)
-    assert _budget(rows, cols, kind, batch, y, ref[kind]) <= eb.cap(rows * cols)
+    rel_l2, _ = budget_run(fft2d, gpu, oracle, rows, cols, kind)
+    assert rel_l2 <= eb.cap(rows * cols)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("rows,cols", SHAPES)
+def test_budget_per_class(fft2d, gpu, oracle, rows, cols, kind):
+    """the same exec: every class of lines and of elements, of the row pass and of the column pass, under the same cap"""
+    _, bad = budget_run(fft2d, gpu, oracle, rows, cols, kind)
+    assert not bad, "\n".join(bad)
+
+
+# ---- the DFT matrix, per output -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows,cols,kind", ss.FFT2D_CASES)
+def test_dft_matrix_sweep(fft2d, gpu, rows, cols, kind):
+    """Fused pairs: batch rows * cols, image b a unit at (b div cols, b mod cols), the full 2-D matrix.  rows = 2 with every
+    width from 64 on (k_rows2d, every tile spanning images) and rows = 64 with every width up to 32 (k_chunk2d<., 0>): batch
+    cols, image b a unit at (b mod rows, b).  Every output within pi / 2^20 and 1e-6 of exp(-+2 pi i (p k / rows + q l / cols))."""
+    x = ss.fft2d_input(rows, cols)
+    bad = ss.fft2d_failures(run(fft2d, gpu, kind, x, rows, cols), rows, cols, kind)
+    assert not bad, "\n".join(bad)
 
 
 # ---- impulses -------------------------------------------------------------------------------------------------------

@@ -9,7 +9,13 @@ is held to numpy.fft.irfft of exactly that.  A reference is computed once per sh
                the split being the last; a radix-2 fp32 model of this algorithm sits at 0.40 - 0.60 of cap(n)
   impulses     pi / 2^20 in angle and 1e-6 in modulus per output of the forward plans; 2 (pi / 2^20 + 1e-6) absolute per
                sample of the inverse plans (two unit-modulus terms, each at that bound)
-Everything else is bit for bit.  With REAL_RECORD=<path> in the environment the budget test also writes the measured
+  per class    test_budget_per_class: the cap of the budget on the rel-L2 of every class of tests/side_sweeps.py's maps
+               (line mod RT or mod 256 / 128, element mod T and div T of the half-length network), on the exec test_budget
+               made
+  sweeps       test_dft_matrix_sweep (tests/side_sweeps.py): a unit at every sample of a forward row, a real unit at every
+               bin and an imaginary unit at every interior bin of an inverse one, at every n, every output at the bounds
+               above
+Everything else is bit for bit.  With REAL_RECORD=<path> in the environment the budget tests also write the measured
 figures there (tests/golden/real_error.json is such a record; no test pins to it).
 """
 import ctypes
@@ -22,6 +28,7 @@ import pytest
 import torch  # before the library: one HIP runtime in the process, the one torch brings (as in bench.py)
 
 import guarded_arena as ga
+import side_sweeps as ss
 from conftest import REL_TOL
 from oracle import error_budget as eb
 from oracle.device_run import open_gpu
@@ -34,6 +41,7 @@ KINDS = ("Forward", "Inverse", "Onlyinverse")
 INVALID_ARG, UNSUPPORTED = 1, 6
 IMPULSE_ANGLE, IMPULSE_MODULUS = np.pi / 2 ** 20, 1e-6
 IMPULSE_ABS = 2 * (IMPULSE_ANGLE + IMPULSE_MODULUS)
+assert (ss.ANGLE, ss.MODULUS, ss.REAL_INVERSE_ABS) == (IMPULSE_ANGLE, IMPULSE_MODULUS, IMPULSE_ABS)
 
 
 def default_batch(n):
@@ -136,25 +144,56 @@ def test_parity(real, gpu, oracle, n, kind):
 
 # ---- budget ---------------------------------------------------------------------------------------------------------
 _measured = {}
+_budget_runs = {}
+
+
+def budget_run(real, gpu, oracle, n, kind):
+    """One exec per (n, kind) at >= 2^18 real samples, shared by the two budget tests: (whole-buffer rel-L2, failures of the
+    per-class check)."""
+    if (n, kind) not in _budget_runs:
+        batch = -(-eb.MIN_SAMPLES // n)
+        x, ref = rows(oracle, n, batch)
+        y = run(real, gpu, kind, x[kind], n).astype(np.complex128 if kind == "Forward" else np.float64)
+        r = ref[kind]
+        rel_l2 = float(np.sqrt((np.abs(y - r) ** 2).sum() / (np.abs(r) ** 2).sum()))
+        print("budget n %d %s batch %d: rel_l2 %.4g = %.3f of the cap %.4g" % (n, kind, batch, rel_l2, rel_l2 / eb.cap(n), eb.cap(n)))
+        bad, spread = ss.class_failures(y, r, ss.real_classes(n, kind, batch), float(eb.cap(n)), "real %s n %d" % (kind, n))
+        _measured["%d/%s" % (n, kind)] = dict({"n": n, "kind": kind, "batch": batch, "rel_l2": rel_l2, "cap": float(eb.cap(n))},
+                                              **ss.spread_record(spread))
+        path = os.environ.get("REAL_RECORD")
+        if path:
+            with open(path, "w") as f:
+                json.dump({"metric": "whole-buffer rel-L2 against numpy.fft.rfft / irfft in float64; per class (tests/side_sweeps.py) "
+                                     "as a fraction of the cap", "cases": _measured}, f, indent=1, sort_keys=True)
+        _budget_runs[(n, kind)] = (rel_l2, bad)
+    return _budget_runs[(n, kind)]
 
 
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("n", LENGTHS)
 def test_budget(real, gpu, oracle, n, kind):
     """>= 2^18 real samples per length: whole-buffer rel-L2 under the cap of n"""
-    batch = -(-eb.MIN_SAMPLES // n)
-    x, ref = rows(oracle, n, batch)
-    y = run(real, gpu, kind, x[kind], n).astype(np.complex128 if kind == "Forward" else np.float64)
-    r = ref[kind]
-    rel_l2 = float(np.sqrt((np.abs(y - r) ** 2).sum() / (np.abs(r) ** 2).sum()))
-    print("budget n %d %s batch %d: rel_l2 %.4g = %.3f of the cap %.4g" % (n, kind, batch, rel_l2, rel_l2 / eb.cap(n), eb.cap(n)))
-    _measured["%d/%s" % (n, kind)] = {"n": n, "kind": kind, "batch": batch, "rel_l2": rel_l2, "cap": float(eb.cap(n))}
-    path = os.environ.get("REAL_RECORD")
-    if path:
-        with open(path, "w") as f:
-            json.dump({"metric": "whole-buffer rel-L2 against numpy.fft.rfft / irfft in float64", "cases": _measured}, f, indent=1,
-                      sort_keys=True)
+    rel_l2, _ = budget_run(real, gpu, oracle, n, kind)
     assert rel_l2 <= eb.cap(n)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("n", LENGTHS)
+def test_budget_per_class(real, gpu, oracle, n, kind):
+    """the same exec: every class of rows (the lane group of a tile, the thread of the small kernel) and of elements (thread
+    and register of the half-length network) under the same cap"""
+    _, bad = budget_run(real, gpu, oracle, n, kind)
+    assert not bad, "\n".join(bad)
+
+
+# ---- the DFT matrix, per output -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,kind", ss.REAL_CASES)
+def test_dft_matrix_sweep(real, gpu, n, kind):
+    """Forward: batch n, row b a unit at b, bins 0 .. n / 2 of every row.  The inverse kinds: batch n, a real unit at every bin,
+    then an imaginary unit at every interior bin; every sample of every row (the scaled kind times n)."""
+    x = ss.real_input(n, kind)
+    bad = ss.real_failures(run(real, gpu, kind, x, n), n, kind)
+    assert not bad, "\n".join(bad)
 
 
 # ---- impulses -------------------------------------------------------------------------------------------------------

@@ -4,8 +4,11 @@ The float64 reference is numpy.fft.fft / ifft on complex128 along the row axis; 
 (batch, n rows, howmany columns).  A reference is computed once per shape and shared by the three plan kinds.  Bounds:
   parity       per column, oracle.compare's max_rel and rel-L2 <= REL_TOL (tests/conftest.py)
   budget       whole-buffer rel-L2 <= oracle.error_budget.cap(n), the one cap of every kernel family
-  impulses     pi / 2^20 in angle and 1e-6 in modulus, the bound of the project's impulse sweeps
-Everything else is bit for bit.  With STRIDED_RECORD=<path> in the environment the budget test also writes the measured
+  per class    test_budget_per_class: the same cap on the rel-L2 of every class of tests/side_sweeps.py's maps (column mod
+               16 / 8 / 256, row mod T and div T), on the exec test_budget made
+  impulses     pi / 2^20 in angle and 1e-6 in modulus, the bound of the project's impulse sweeps; test_dft_matrix_sweep
+               (tests/side_sweeps.py) reads the whole DFT matrix out of every kernel, every kind, every n, per output
+Everything else is bit for bit.  With STRIDED_RECORD=<path> in the environment the budget tests also write the measured
 figures there (tests/golden/strided_error.json is such a record; no test pins to it).
 """
 import ctypes
@@ -18,6 +21,7 @@ import pytest
 import torch  # before the library: one HIP runtime in the process, the one torch brings (as in bench.py)
 
 import guarded_arena as ga
+import side_sweeps as ss
 from conftest import REL_TOL
 from oracle import error_budget as eb
 from oracle.device_run import open_gpu
@@ -106,25 +110,56 @@ def test_parity(strided, gpu, oracle, n, kind):
 
 # ---- budget ---------------------------------------------------------------------------------------------------------
 _measured = {}
+_budget_runs = {}
+
+
+def budget_run(strided, gpu, oracle, n, kind):
+    """One exec per (n, kind) at >= 2^18 samples (the smallest power-of-two howmany, one matrix), shared by the two budget
+    tests: (whole-buffer rel-L2, failures of the per-class check)."""
+    if (n, kind) not in _budget_runs:
+        howmany = eb.MIN_SAMPLES // n
+        x, ref = matrices(oracle, n, howmany, 1)
+        y = run(strided, gpu, kind, x, n, howmany)
+        r = ref[kind]
+        rel_l2 = float(np.sqrt((np.abs(y - r) ** 2).sum() / (np.abs(r) ** 2).sum()))
+        print("budget n=%d %s howmany=%d: rel_l2 %.4g = %.3f of the cap %.4g" % (n, kind, howmany, rel_l2, rel_l2 / eb.cap(n), eb.cap(n)))
+        bad, spread = ss.class_failures(y, r, ss.strided_classes(n, howmany), float(eb.cap(n)), "strided %s n %d" % (kind, n))
+        _measured["%d/%s" % (n, kind)] = dict({"n": n, "kind": kind, "howmany": howmany, "batch": 1, "rel_l2": rel_l2,
+                                               "cap": float(eb.cap(n))}, **ss.spread_record(spread))
+        path = os.environ.get("STRIDED_RECORD")
+        if path:
+            with open(path, "w") as f:
+                json.dump({"metric": "whole-buffer rel-L2 against numpy.fft in float64; per class (tests/side_sweeps.py) as a "
+                                     "fraction of the cap", "cases": _measured}, f, indent=1, sort_keys=True)
+        _budget_runs[(n, kind)] = (rel_l2, bad)
+    return _budget_runs[(n, kind)]
 
 
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("n", LENGTHS)
 def test_budget(strided, gpu, oracle, n, kind):
     """>= 2^18 samples per shape (the smallest power-of-two howmany, one matrix): whole-buffer rel-L2 under the cap."""
-    howmany = eb.MIN_SAMPLES // n
-    x, ref = matrices(oracle, n, howmany, 1)
-    y = run(strided, gpu, kind, x, n, howmany)
-    r = ref[kind]
-    rel_l2 = float(np.sqrt((np.abs(y - r) ** 2).sum() / (np.abs(r) ** 2).sum()))
-    print("budget n=%d %s howmany=%d: rel_l2 %.4g = %.3f of the cap %.4g" % (n, kind, howmany, rel_l2, rel_l2 / eb.cap(n), eb.cap(n)))
-    _measured["%d/%s" % (n, kind)] = {"n": n, "kind": kind, "howmany": howmany, "batch": 1, "rel_l2": rel_l2,
-                                       "cap": float(eb.cap(n))}
-    path = os.environ.get("STRIDED_RECORD")
-    if path:
-        with open(path, "w") as f:
-            json.dump({"metric": "whole-buffer rel-L2 against numpy.fft in float64", "cases": _measured}, f, indent=1, sort_keys=True)
+    rel_l2, _ = budget_run(strided, gpu, oracle, n, kind)
     assert rel_l2 <= eb.cap(n)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("n", LENGTHS)
+def test_budget_per_class(strided, gpu, oracle, n, kind):
+    """the same exec: every class of columns (the lane group of a tile) and of rows (thread and register of the network)
+    under the same cap"""
+    _, bad = budget_run(strided, gpu, oracle, n, kind)
+    assert not bad, "\n".join(bad)
+
+
+# ---- the DFT matrix, per output -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,kind", ss.STRIDED_CASES)
+def test_dft_matrix_sweep(strided, gpu, n, kind):
+    """one matrix of n rows x (n + 5) columns, column c a unit at row c: the output columns are the DFT matrix (/ n for
+    Inverse), every entry within pi / 2^20 and 1e-6; the five zero columns, a partial last tile at every n, stay zero"""
+    x = ss.strided_input(n)
+    bad = ss.strided_failures(run(strided, gpu, kind, x, n, n + ss.ZERO_COLUMNS), n, kind)
+    assert not bad, "\n".join(bad)
 
 
 # ---- round trip -----------------------------------------------------------------------------------------------------
@@ -228,10 +263,12 @@ def test_nan_stays_in_its_column_and_powers_of_two_scale_exactly(strided, gpu, o
 
 
 # ---- past 4 GiB -----------------------------------------------------------------------------------------------------
-def _impulse_failures(strided, gpu, n, howmany, impulses, rows, windows):
-    """One zeroed matrix with a unit impulse at (j0, c) for every c: j0 of `impulses`; Forward; in every window (first
-    column, count) of every row of `rows`: the impulse columns hold exp(-2 pi i j0 k / n) within pi / 2^20 in angle and
-    1e-6 in modulus, every other column is exactly zero."""
+def _impulse_failures(strided, gpu, n, howmany, impulses, rows, windows, kind="Forward"):
+    """One zeroed matrix with a unit impulse at (j0, c) for every c: j0 of `impulses`; one exec of `kind`; in every window
+    (first column, count) of every row of `rows`: the impulse columns hold exp(-+2 pi i j0 k / n) (/ n for Inverse: the
+    exact power of two is taken off first) within pi / 2^20 in angle and 1e-6 in modulus, every other column is exactly
+    zero."""
+    sign, scale = (-1.0 if kind == "Forward" else 1.0), (float(n) if kind == "Inverse" else 1.0)
     fw, dev, queue = gpu
     row_bytes = howmany * 8
     t = torch.zeros(n * howmany, dtype=torch.complex64, device="cuda")       # zeroed on the device
@@ -241,7 +278,7 @@ def _impulse_failures(strided, gpu, n, howmany, impulses, rows, windows):
     for c, j0 in impulses.items():
         queue.write_buffer(buf, j0 * row_bytes + c * 8, one)
     enc = dev.create_command_encoder()
-    plan = strided.Forward(dev, queue, buf, n, howmany)
+    plan = getattr(strided, kind)(dev, queue, buf, n, howmany)
     per_wg = plan.get("tile_cols") * (512 // n if n <= 32 else 1)
     assert plan.get("batch") == 1 and plan.get("blocks") == -(-howmany // per_wg)
     plan.proc(enc)
@@ -251,9 +288,9 @@ def _impulse_failures(strided, gpu, n, howmany, impulses, rows, windows):
             y = buf.map_read(offset=k * row_bytes + c0 * 8, size=count * 8, stream=enc)
             cols = np.array(sorted(c for c in impulses if c0 <= c < c0 + count))
             assert cols.size
-            got = y[cols - c0].astype(np.complex128)
+            got = y[cols - c0].astype(np.complex128) * scale
             j0 = np.array([impulses[c] for c in cols])
-            want = np.exp(-2j * np.pi * ((j0 * k) % n) / n)
+            want = np.exp(sign * 2j * np.pi * ((j0 * k) % n) / n)
             angle = np.abs(np.angle(got * np.conj(want)))
             modulus = np.abs(np.abs(got) - 1.0)
             if not (angle.max() <= np.pi / 2 ** 20 and modulus.max() <= 1e-6):
@@ -289,16 +326,18 @@ def test_matrix_past_4gib(strided, gpu):
     assert not bad, "\n".join(bad)
 
 
-@pytest.mark.parametrize("n", [16, 64, 1024])
-def test_matrix_past_2gib_takes_the_64bit_pointer_kernels(strided, gpu, n):
-    """A matrix of more than 2^31 bytes leaves the one-descriptor form of every kernel shape (one column per thread, two
-    stages; three stages: the 4-GiB case above).  Same check, in three windows of 4096 columns of four rows."""
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("n", [2, 16, 64, 1024, 2048])
+def test_matrix_past_2gib_takes_the_64bit_pointer_kernels(strided, gpu, n, kind):
+    """A matrix of more than 2^31 bytes leaves the one-descriptor form of every kernel shape, in every kind (one column per
+    thread, with 16 steps per workgroup at n = 2 and 2 at n = 16; two stages; three stages of 16 columns at 2048; three
+    stages of 8 columns: the 4-GiB case above).  Same check, in three windows of 4096 columns of four rows."""
     howmany = (1 << 31) // (8 * n) + 5
     assert 8 * n * howmany > 1 << 31
     mid = howmany // 2
     impulses = {0: 0, 15: n - 1, 16: 1, mid + 1: n // 2, mid + 40: n - 1, howmany - 3: n - 1, howmany - 1: 1}
     windows = [(0, 4096), (mid - 2048, 4096), (howmany - 4096, 4096)]
-    bad = _impulse_failures(strided, gpu, n, howmany, impulses, (0, 1, n // 2, n - 1), windows)
+    bad = _impulse_failures(strided, gpu, n, howmany, impulses, (0, 1, n // 2, n - 1), windows, kind)
     assert not bad, "\n".join(bad)
 
 
