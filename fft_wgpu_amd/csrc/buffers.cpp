@@ -98,10 +98,11 @@ static int32_t peer_kind(fwa_ctx *a, fwa_ctx *b, int32_t *kind)
     for (fwa_ctx *c : {a, b}) {
         fwa_ctx *o = c == a ? b : a;
         if (std::find(c->peers_enabled.begin(), c->peers_enabled.end(), o->device) != c->peers_enabled.end()) continue;
-        HIP_TRY(c, hipSetDevice(c->device));
+        // (errors go to `a`, the context the caller passed first and reads the detail from, also when `b`'s device refuses)
+        HIP_TRY(a, hipSetDevice(c->device));
         hipError_t e = hipDeviceEnablePeerAccess(o->device, 0);
         if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
-            return fail_hip(c, e, "hipDeviceEnablePeerAccess");
+            return fail_hip(a, e, "hipDeviceEnablePeerAccess");
         (void)hipGetLastError();
         c->peers_enabled.push_back(o->device);
     }

@@ -238,7 +238,8 @@ int32_t fwa_ctx_create(int32_t device_ordinal, fwa_ctx **out)
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess || n <= 0)
         return fail(nullptr, FWA_ERR_NO_DEVICE,
-                    std::string("no HIP device visible: ") + (e != hipSuccess ? hipGetErrorString(e) : "count = 0"));
+                    std::string("no HIP device visible: ") +
+                        (e != hipSuccess ? std::string("hipGetDeviceCount: ") + hipGetErrorString(e) : std::string("count = 0")));
     if (device_ordinal < 0 || device_ordinal >= n)
         return fail(nullptr, FWA_ERR_INVALID_ARG, "device ordinal out of range");
     fwa_ctx *ctx = new (std::nothrow) fwa_ctx;

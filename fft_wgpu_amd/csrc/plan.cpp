@@ -133,7 +133,13 @@ static int32_t run_groups(fwa_plan *plan, hipStream_t st, Body body)
     for (size_t i = 0; i < ns; ++i) {
         hipError_t r = hipEventRecord(pl.done[i], pl.streams[i]);
         if (r == hipSuccess) r = hipStreamWaitEvent(st, pl.done[i], 0);
-        if (r != hipSuccess && je == hipSuccess) je = r;
+        if (r != hipSuccess) {
+            // no event carries the order: the host waits for this chain instead, so that whatever is enqueued on `st`
+            // after this call still comes behind it
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(pl.streams[i]);
+            if (je == hipSuccess) je = r;
+        }
     }
     plan->last_stream = st;
     plan->ran_on_stream = true;
@@ -266,6 +272,7 @@ int32_t fwa_plan_destroy(fwa_plan *plan)
     // for, through a marker on the stream that exec was enqueued on -- other streams and contexts keep running (a
     // device-wide synchronise here stalled them all and is illegal while any stream captures a graph).  An exec that
     // was captured into a graph enqueued nothing real: the plan must outlive the graphs that replay it.
+    bool drained = true;
     if (plan->frozen && plan->pipe.ring) {
         hipEvent_t ev = nullptr;
         bool waited = false;
@@ -285,10 +292,12 @@ int32_t fwa_plan_destroy(fwa_plan *plan)
         if (!waited) {
             (void)hipGetLastError();
             // the stream is gone or not ours (fwa_stream_wrap), or a laboratory persistent path
-            (void)hipDeviceSynchronize();
+            drained = hipDeviceSynchronize() == hipSuccess;
+            if (!drained) (void)hipGetLastError();
         }
     }
-    release_pipeline(plan->ctx, plan->pipe, true);
+    // a ring that may still be in use is not pooled: it is freed, and hipFree synchronises
+    release_pipeline(plan->ctx, plan->pipe, drained);
     if (plan->tw_half_private) (void)hipFree(plan->tw_half_private);
     if (plan->second_owned && plan->own_second.p) (void)hipFree(plan->own_second.p);
     delete plan;

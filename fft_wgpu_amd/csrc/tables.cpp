@@ -25,7 +25,14 @@ int32_t upload_table(fwa_ctx *ctx, const std::vector<v2f> &h, v2f **d)
     *d = nullptr;
     if (h.empty()) return FWA_OK;
     HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(d), h.size() * sizeof(v2f)));
-    HIP_TRY(ctx, hipMemcpy(*d, h.data(), h.size() * sizeof(v2f), hipMemcpyHostToDevice));
+    // a table that was never written must not stay behind in *d: callers keep the pointer in long-lived fields
+    // (fwa_plan::tw_half_private) and take "non-null" for "uploaded"
+    hipError_t e = hipMemcpy(*d, h.data(), h.size() * sizeof(v2f), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(*d);
+        *d = nullptr;
+        return fail_hip(ctx, e, "hipMemcpy(twiddle table)");
+    }
     return FWA_OK;
 }
 
@@ -170,12 +177,12 @@ int32_t build_pipeline(fwa_plan *p, int64_t group, int64_t n_streams)
     if (pl.ring_bytes && n_streams > 1) {
         if (int32_t cs = chain_streams(ctx, (size_t)n_streams)) return finish(cs);
         hipError_t e = hipEventCreateWithFlags(&pl.fork, hipEventDisableTiming);
-        if (e != hipSuccess) { pl.fork = nullptr; return finish(fail_hip(ctx, e, "hipEventCreate")); }
+        if (e != hipSuccess) { pl.fork = nullptr; return finish(fail_hip(ctx, e, "hipEventCreateWithFlags")); }
         for (int64_t i = 0; i < n_streams; ++i) {
             hipEvent_t ev;
             pl.streams.push_back(ctx->chains[(size_t)i]);
             e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-            if (e != hipSuccess) return finish(fail_hip(ctx, e, "hipEventCreate"));
+            if (e != hipSuccess) return finish(fail_hip(ctx, e, "hipEventCreateWithFlags"));
             pl.done.push_back(ev);
         }
     }

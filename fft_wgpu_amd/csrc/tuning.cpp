@@ -68,7 +68,7 @@ int32_t fwa_plan_get_i64(const fwa_plan *plan, const char *key, int64_t *value)
             case PATH_RING_1M: *value = 1; break;
             case PATH_TILED: *value = resolve_tiled(plan->lg, plan->lf, plan->flags).passes * ng; break;
             case PATH_R2_GLOBAL: *value = plan->lg; break;
-            case PATH_IDENTITY: *value = (plan->kind == FWA_INVERSE_SCALED) ? 1 : 0; break;
+            case PATH_IDENTITY: *value = 0; break;   // n = 1: also the scaled inverse's 1/n is 1, and exec launches nothing
             default: *value = 1;
         }
     } else return fail(plan->ctx, FWA_ERR_INVALID_ARG, "unknown key: " + k);
