@@ -14,6 +14,7 @@ from . import strided  # noqa: F401  (column transforms of row-major matrices; i
 from . import fft2d  # noqa: F401  (in-place 2-D transforms of batched row-major images; likewise)
 from . import real  # noqa: F401  (rfft / irfft of batched real rows, out of place; likewise)
 from . import conv  # noqa: F401  (ifft(fft(x) * H) of batched rows in one launch; likewise)
+from . import stft  # noqa: F401  (rfft of overlapping, windowed frames of real signals in one launch; likewise)
 
 COMPLEX_BYTES = 8  # src/lib.rs:10-15: {real: f32, imag: f32}
 
