@@ -20,10 +20,14 @@
 
 #include "internal.h"
 
-struct fwa_comm {
-    fwa_ctx *ctx = nullptr;
+// A communicator is a handle of its context like a stream, a buffer or an event (handles.h): fwa_ctx_destroy detaches
+// it, `ctx` is nullptr from then on, every entry point but fwa_comm_destroy and fwa_comm_get_i64 refuses it, and
+// nothing here reads the context's memory after that.  The registry knows three kinds, enumerates streams and counts streams
+// and buffers; a communicator is listed under the kind nothing enumerates or counts.
+struct fwa_comm : fwa_int::Handle {
     ncclComm_t comm = nullptr;
     int32_t world = 0, rank = 0;
+    int device = -1;  // for fwa_comm_destroy and "device" after the context is gone
 };
 
 namespace {
@@ -92,6 +96,16 @@ std::string ipc_mode_hint()
            "is in the environment before the HIP runtime loads (include/fft_wgpu_amd.h, fwa_comm)";
 }
 
+// An RCCL failure where peers are set up or first used (communicator creation, any step of an exchange) gets the
+// sentence about the one misconfiguration this library has met in the field: hosts whose driver only supports dmabuf
+// IPC (include/fft_wgpu_amd.h, fwa_comm block).  `rc` is what fail_nccl has just recorded on ctx.
+int32_t with_ipc_hint(const fwa_ctx *ctx, int32_t rc)
+{
+    const std::string hint = ipc_mode_hint();
+    if (!hint.empty()) (void)fwa_int::fail(ctx, rc, std::string(fwa_last_error_string(ctx)) + hint);
+    return rc;
+}
+
 static_assert(sizeof(ncclUniqueId) == FWA_COMM_ID_BYTES, "FWA_COMM_ID_BYTES must be sizeof(ncclUniqueId)");
 
 struct Piece {  // one side of a point-to-point transfer: bytes at ptr, to / from `peer` (-1: none)
@@ -105,6 +119,34 @@ bool in_range(const fwa_buf *b, uint64_t off, uint64_t bytes) { return off <= fw
                                                                && bytes <= fwa_buf_size(b) - off; }
 char *at(const fwa_buf *b, uint64_t off) { return static_cast<char *>(fwa_buf_device_ptr(b)) + off; }
 
+// RCCL takes a buffer as a pointer under the communicator's device: one of another context, or of a destroyed one
+// (whose memory its own fwa_buf_free releases, possibly already), must not get there
+int32_t check_buf(const fwa_ctx *ctx, const fwa_buf *b, const char *name)
+{
+    if (!b->ctx)
+        return fwa_int::fail(ctx, FWA_ERR_INVALID_ARG,
+                             std::string(name) + " belongs to a context that has been destroyed");
+    if (b->ctx != ctx)
+        return fwa_int::fail(ctx, FWA_ERR_INVALID_ARG, std::string(name) + " belongs to another context");
+    return FWA_OK;
+}
+int32_t check_stream(const fwa_ctx *ctx, const fwa_stream *s)
+{
+    if (!s) return FWA_OK;
+    if (!s->ctx)
+        return fwa_int::fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to a context that has been destroyed");
+    if (s->ctx != ctx) return fwa_int::fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to another context");
+    return FWA_OK;
+}
+// every collective starts here: nullptr, with the error recorded, for a communicator whose context has been destroyed
+fwa_ctx *live_ctx(const fwa_comm *c)
+{
+    if (!c->ctx)
+        (void)fwa_int::fail(nullptr, FWA_ERR_INVALID_ARG,
+                            "the communicator belongs to a context that has been destroyed");
+    return c->ctx;
+}
+
 // Grouped sends and receives of this rank on `stream`; a piece addressed to the rank itself must have its partner in
 // the same group (RCCL pairs them up as a local copy).
 int32_t exchange(fwa_comm *c, const Piece *sends, size_t ns, const Piece *recvs, size_t nr, fwa_stream *stream)
@@ -115,7 +157,7 @@ int32_t exchange(fwa_comm *c, const Piece *sends, size_t ns, const Piece *recvs,
     USE_DEVICE(c->ctx);
     hipStream_t hs = fwa_int::raw(stream);
     ncclResult_t e = r->GroupStart();
-    if (e != ncclSuccess) return fail_nccl(c->ctx, r, e, "ncclGroupStart");
+    if (e != ncclSuccess) return with_ipc_hint(c->ctx, fail_nccl(c->ctx, r, e, "ncclGroupStart"));
     for (size_t i = 0; i < ns && e == ncclSuccess; ++i)
         if (sends[i].peer >= 0 && sends[i].bytes) e = r->Send(sends[i].ptr, sends[i].bytes, ncclInt8, sends[i].peer,
                                                               c->comm, hs);
@@ -123,13 +165,9 @@ int32_t exchange(fwa_comm *c, const Piece *sends, size_t ns, const Piece *recvs,
         if (recvs[i].peer >= 0 && recvs[i].bytes) e = r->Recv(recvs[i].ptr, recvs[i].bytes, ncclInt8, recvs[i].peer,
                                                               c->comm, hs);
     const ncclResult_t ge = r->GroupEnd();
-    if (e != ncclSuccess || ge != ncclSuccess) {
-        const int32_t rc = e != ncclSuccess ? fail_nccl(c->ctx, r, e, "ncclSend/ncclRecv")
-                                            : fail_nccl(c->ctx, r, ge, "ncclGroupEnd");
-        const std::string hint = ipc_mode_hint();   // peers are mapped on the first exchange
-        if (!hint.empty()) (void)fwa_int::fail(c->ctx, rc, std::string(fwa_last_error_string(c->ctx)) + hint);
-        return rc;
-    }
+    if (e != ncclSuccess || ge != ncclSuccess)  // peers are mapped on the first exchange
+        return with_ipc_hint(c->ctx, e != ncclSuccess ? fail_nccl(c->ctx, r, e, "ncclSend/ncclRecv")
+                                                      : fail_nccl(c->ctx, r, ge, "ncclGroupEnd"));
     return FWA_OK;
 }
 
@@ -168,14 +206,10 @@ int32_t fwa_comm_create(fwa_ctx *ctx, const uint8_t id[FWA_COMM_ID_BYTES], int32
     const ncclResult_t e = r->CommInitRank(&c->comm, world, u, rank);
     if (e != ncclSuccess) {
         delete c;
-        const int32_t rc = fail_nccl(ctx, r, e, "ncclCommInitRank");
-        // the one misconfiguration this library has met in the field: hosts whose driver only supports dmabuf IPC
-        // (include/fft_wgpu_amd.h, fwa_comm block)
-        const std::string hint = ipc_mode_hint();
-        if (!hint.empty()) (void)fwa_int::fail(ctx, rc, std::string(fwa_last_error_string(ctx)) + hint);
-        return rc;
+        return with_ipc_hint(ctx, fail_nccl(ctx, r, e, "ncclCommInitRank"));
     }
-    c->ctx = ctx; c->world = world; c->rank = rank;
+    c->world = world; c->rank = rank; c->device = ctx->device;
+    fwa_int::attach(ctx, ctx->handles, c, fwa_int::H_EVENT);  // (the kind nothing enumerates or counts: see fwa_comm)
     *out = c;
     return FWA_OK;
 }
@@ -184,8 +218,9 @@ int32_t fwa_comm_destroy(fwa_comm *comm)
 {
     if (!comm) return FWA_OK;
     Rccl *r = rccl();
+    fwa_int::detach(comm);
     if (comm->comm && r->CommDestroy) {
-        (void)hipSetDevice(comm->ctx->device);
+        (void)hipSetDevice(comm->device);
         (void)r->CommDestroy(comm->comm);
     }
     delete comm;
@@ -198,7 +233,7 @@ int32_t fwa_comm_get_i64(const fwa_comm *comm, const char *key, int64_t *value)
     const std::string k(key);
     if (k == "rank") *value = comm->rank;
     else if (k == "world") *value = comm->world;
-    else if (k == "device") *value = comm->ctx->device;
+    else if (k == "device") *value = comm->device;  // the communicator's own copy: valid after its context too
     else return fwa_int::fail(comm->ctx, FWA_ERR_INVALID_ARG, "unknown key: " + k);
     return FWA_OK;
 }
@@ -209,7 +244,8 @@ int32_t fwa_comm_sendrecv(fwa_comm *comm, const fwa_buf *send, uint64_t send_off
                               fwa_stream *stream)
 {
     if (!comm) return fwa_int::fail(nullptr, FWA_ERR_INVALID_ARG, "comm is NULL");
-    fwa_ctx *ctx = comm->ctx;
+    fwa_ctx *ctx = live_ctx(comm);
+    if (!ctx) return FWA_ERR_INVALID_ARG;
     if (send_to >= comm->world || recv_from >= comm->world)
         return fwa_int::fail(ctx, FWA_ERR_INVALID_ARG, "peer rank out of range");
     if (send_to >= 0 && (!send || !in_range(send, send_offset, send_bytes)))
@@ -219,8 +255,11 @@ int32_t fwa_comm_sendrecv(fwa_comm *comm, const fwa_buf *send, uint64_t send_off
     if ((send_to == comm->rank) != (recv_from == comm->rank) || (send_to == comm->rank && send_bytes != recv_bytes))
         return fwa_int::fail(ctx, FWA_ERR_INVALID_ARG,
                              "a send to this rank itself needs the matching receive in the same call");
-    if (stream && stream->ctx != ctx)
-        return fwa_int::fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to another context");
+    if (send_to >= 0)
+        if (int32_t st = check_buf(ctx, send, "the send buffer")) return st;
+    if (recv_from >= 0)
+        if (int32_t st = check_buf(ctx, recv, "the receive buffer")) return st;
+    if (int32_t st = check_stream(ctx, stream)) return st;
     const Piece s{send_to >= 0 ? at(send, send_offset) : nullptr, send_bytes, send_to};
     const Piece r{recv_from >= 0 ? at(recv, recv_offset) : nullptr, recv_bytes, recv_from};
     return exchange(comm, &s, 1, &r, 1, stream);
@@ -267,10 +306,11 @@ int32_t move_slabs(fwa_comm *comm, bool gather, int32_t root, const fwa_buf *sla
 {
     if (!comm || !slab || !fft_len)
         return fwa_int::fail(comm ? comm->ctx : nullptr, FWA_ERR_INVALID_ARG, "comm/slab is NULL or fft_len is 0");
-    fwa_ctx *ctx = comm->ctx;
+    fwa_ctx *ctx = live_ctx(comm);
+    if (!ctx) return FWA_ERR_INVALID_ARG;
     if (root < 0 || root >= comm->world) return fwa_int::fail(ctx, FWA_ERR_INVALID_ARG, "root out of range");
-    if (stream && stream->ctx != ctx)
-        return fwa_int::fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to another context");
+    if (int32_t st = check_stream(ctx, stream)) return st;
+    if (int32_t st = check_buf(ctx, slab, "the slab buffer")) return st;
     const bool is_root = comm->rank == root;
     std::vector<uint64_t> off((size_t)(is_root ? comm->world : 1)), len(off.size());
     std::vector<int32_t> peer(off.size());
@@ -289,6 +329,7 @@ int32_t move_slabs(fwa_comm *comm, bool gather, int32_t root, const fwa_buf *sla
     }
     if (!full || !in_range(full, 0, batch * tb))
         return fwa_int::fail(ctx, FWA_ERR_INVALID_ARG, "root needs the full batch buffer");
+    if (int32_t st = check_buf(ctx, full, "the full batch buffer")) return st;
     std::vector<Piece> pieces((size_t)np);
     for (int32_t p = 0; p < np; ++p) pieces[(size_t)p] = Piece{at(full, off[(size_t)p]), len[(size_t)p],
                                                                peer[(size_t)p]};

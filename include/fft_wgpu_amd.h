@@ -36,7 +36,8 @@
  * of the context captures a graph; fwa_ctx_set_i64(ctx, "chain_check", 0)
  * turns the check off.
  *
- * Lifetimes: plans and communicators go before their context, buffers before the plans that use them.  Buffer, stream
+ * Lifetimes: plans go before their context, buffers before the plans that use them.  A communicator should go before its
+ * context too, but is held like a handle (see fwa_comm below for what it answers afterwards).  Buffer, stream
  * and event HANDLES may be destroyed after their context (hosts with garbage collection free in any order): the context
  * keeps a list of its live handles and detaches them in fwa_ctx_destroy, so USING one afterwards -- upload, download,
  * copy, plan creation, event record ... -- returns FWA_ERR_INVALID_ARG; it never touches freed memory.  That list has one
@@ -264,6 +265,17 @@ int32_t fwa_plan_set_i64(fwa_plan *plan, const char *key, int64_t value);
  * the matching sends / receives and will wait on their streams for ever -- there is no timeout.  Validate sizes before
  * the call on every rank; after a failure destroy the communicator on every rank (and the processes with it, if peers
  * are already blocked).  These calls allocate a few small host vectors on the root; fwa_plan_exec never allocates.
+ * What is rejected with FWA_ERR_INVALID_ARG before anything is posted: a peer or root outside the world; a range past its
+ * buffer; a send to the own rank without the receive of the same size (or the reverse); a `send`, `recv`, `slab` or `full`
+ * buffer, or a stream, that belongs to another context than the communicator's or to a context that has been destroyed
+ * (RCCL would take the buffer as a pointer under the communicator's device); a slab buffer smaller than the rank's slab; a
+ * root without a full buffer of `batch` transforms.  A failure inside RCCL is FWA_ERR_HIP: the error text names the
+ * RCCL call, carries the sentence about HSA_ENABLE_IPC_MODE_LEGACY unless the variable is "0", and the group the call
+ * opened is closed.
+ * Order of destruction: a communicator is listed with its context like a buffer, stream or event handle.  Destroy it before
+ * its context.  If the context goes first, fwa_comm_get_i64 still answers ("rank", "world" and "device" are the
+ * communicator's own), fwa_comm_scatter / gather / sendrecv return FWA_ERR_INVALID_ARG, and fwa_comm_destroy releases the
+ * RCCL communicator on its device and returns FWA_OK; freed memory is never touched.
  * fwa_comm_pieces: pure host logic, no device and no RCCL needed -- the point-to-point pieces rank `rank` posts in a
  * scatter or gather of `batch` transforms rooted at `root` (the table both collectives are built on; arrays of `world`
  * entries): a non-root rank posts one piece (offset 0 into its slab buffer, its whole slab, peer = root), the root posts

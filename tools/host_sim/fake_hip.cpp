@@ -2,7 +2,7 @@
 // objects (fft_wgpu_amd/csrc/*.cpp and the four side-library hosts) leave undefined, with the real hip_runtime_api.h for
 // types and signatures.  A missing entry point is a link error: that is the completeness check.
 //
-// Two devices.  Device memory is address space only: hipMalloc is a bump allocator over a range nothing maps, every
+// Eight devices.  Device memory is address space only: hipMalloc is a bump allocator over a range nothing maps, every
 // allocation keeps its device, base, size, liveness, the set of bytes written so far and the accesses made to it.  Streams
 // and events are counted handles; every stream carries a vector clock, hipEventRecord snapshots it, hipStreamWaitEvent
 // merges the snapshot, the synchronising calls merge into the host's clock, and the host's clock goes into every
@@ -19,8 +19,8 @@
 namespace sim {
 namespace {
 
-constexpr int N_DEV = 2;
-constexpr uint64_t DEV_BASE[N_DEV] = {0x200000000000ull, 0x600000000000ull};  // 64 TiB of addresses each, never mapped
+constexpr int N_DEV = 8;
+constexpr uint64_t dev_base(int d) { return 0x200000000000ull + (uint64_t)d * 0x400000000000ull; }  // 64 TiB of addresses each, never mapped
 constexpr uint64_t HBM_BYTES = 288ull << 30;
 constexpr uint64_t ALIGN = 256, GUARD = 4096;
 
@@ -45,11 +45,11 @@ struct Event { int dev = 0; bool live = true, orphan = false, recorded = false; 
 
 struct Books {
     int current = 0;
-    bool peer[N_DEV][N_DEV] = {{false, false}, {false, false}};
-    uint64_t bump[N_DEV] = {0, 0}, live_bytes[N_DEV] = {0, 0};
+    bool peer[N_DEV][N_DEV] = {};
+    uint64_t bump[N_DEV] = {}, live_bytes[N_DEV] = {};
     std::map<uint64_t, Alloc> allocs;            // by base; dead ones stay (addresses are never handed out twice)
     std::map<void *, bool> pinned;               // pointer -> orphan
-    std::vector<Stream> streams;                 // [0], [1]: the null streams of the two devices
+    std::vector<Stream> streams;                 // [0 .. N_DEV): the null streams of the devices
     std::map<hipStream_t, int> stream_of;
     std::vector<Event> events;
     std::map<hipEvent_t, int> event_of;
@@ -69,6 +69,7 @@ struct Books {
     std::vector<float> elapsed;
     size_t elapsed_next = 0;
     float elapsed_then = 0.04f;
+    uint64_t grid = 0;
 };
 Books *g = nullptr;
 std::map<std::string, Coverage> g_cov;  // whole process
@@ -241,7 +242,7 @@ hipError_t copy(const char *name, void *dst, int dst_dev, const void *src, int s
 const char *kind_name(int k)
 {
     static const char *names[V_KINDS] = {"double-free", "out-of-bounds", "unwritten-read", "hazard", "leak", "dead-handle",
-                                         "block-overlap", "check"};
+                                         "block-overlap", "check", "unmatched", "group-open", "size-mismatch", "comm-init"};
     return k >= 0 && k < V_KINDS ? names[k] : "?";
 }
 void violation(int kind, const std::string &what)
@@ -258,6 +259,19 @@ uint64_t violations_total()
     return n;
 }
 const std::vector<std::string> &violation_log() { return B().log; }
+void expect_violations(int kind, uint64_t n, const std::string &why)
+{
+    Books &b = B();
+    if (b.viol[kind] != n) {
+        violation(V_CHECK, why + ": expected " + std::to_string(n) + " x " + kind_name(kind) + ", the books hold " + std::to_string(b.viol[kind]));
+        return;
+    }
+    b.viol[kind] = 0;
+    const std::string prefix = std::string(kind_name(kind)) + ": ";
+    for (size_t i = 0; i < b.log.size();)
+        if (b.log[i].compare(0, prefix.size(), prefix) == 0) b.log.erase(b.log.begin() + (std::ptrdiff_t)i);
+        else ++i;
+}
 
 void reset()
 {
@@ -271,6 +285,7 @@ void reset()
         s.id = d; s.dev = d;
         g->streams.push_back(s);
     }
+    rccl_reset();
 }
 
 void arm(int64_t k, hipError_t error)
@@ -383,6 +398,7 @@ void audit_leaks()
         if (s.id >= N_DEV && s.live && !s.orphan) violation(V_LEAK, "stream " + std::to_string(s.id) + " is still live");
     for (size_t i = 0; i < b.events.size(); ++i)
         if (b.events[i].live && !b.events[i].orphan) violation(V_LEAK, "event " + std::to_string(i) + " is still live");
+    rccl_audit_leaks();
 }
 
 // ---- launches ----
@@ -460,6 +476,41 @@ bool locate(uint64_t addr, uint64_t *base, uint64_t *size)
     *base = a->base; *size = a->size;
     return true;
 }
+void note_grid(uint64_t blocks) { B().grid = blocks; }
+uint64_t last_grid() { return B().grid; }
+int current_device() { return B().current; }
+
+bool post(const char *who, hipStream_t st, Post *out)
+{
+    Books &b = B();
+    Stream *s = stream(st, who);
+    if (!s) return false;
+    if (s->dev != b.current) violation(V_CHECK, std::string(who) + ": posted on a stream of a device that is not current");
+    out->tick = begin_op(*s);
+    out->sid = s->id; out->dev = b.current; out->clock = s->vc;
+    return true;
+}
+
+void transfer(const std::string &name, const Post &src, uint64_t src_addr, const Post &dst, uint64_t dst_addr, uint64_t bytes)
+{
+    Books &b = B();
+    VC when = src.clock;
+    merge(when, dst.clock);
+    // the two sides as the streams they were posted on, at their posted ticks, both knowing what either stream knew
+    Stream from, to;
+    from.id = src.sid; from.dev = src.dev; from.vc = when;
+    to.id = dst.sid; to.dev = dst.dev; to.vc = when;
+    Op op{name, nullptr, dst.sid, dst.tick, {}, {}, false};
+    touch(op, src_addr, src_addr + bytes, false, from, src.tick);
+    touch(op, dst_addr, dst_addr + bytes, true, to, dst.tick);
+    for (const Range &r : op.writes)
+        if (Alloc *a = find_alloc(r.lo)) set_written(*a, r.lo, r.hi);
+    b.ops.push_back(op);
+    // everything later on either stream is behind the transfer
+    merge(b.streams[(size_t)src.sid].vc, when);
+    merge(b.streams[(size_t)dst.sid].vc, when);
+}
+
 bool all_before_marker(size_t first, hipStream_t caller, std::string *which)
 {
     Books &b = B();
@@ -605,7 +656,7 @@ hipError_t hipMalloc(void **p, size_t bytes)
     const int d = b.current;
     if (b.live_bytes[d] + bytes > HBM_BYTES) return err(hipErrorOutOfMemory);
     Alloc a;
-    a.dev = d; a.base = DEV_BASE[d] + b.bump[d]; a.size = bytes;
+    a.dev = d; a.base = dev_base(d) + b.bump[d]; a.size = bytes;
     b.bump[d] += (bytes + GUARD + ALIGN - 1) / ALIGN * ALIGN;
     b.live_bytes[d] += bytes;
     b.allocs[a.base] = a;

@@ -21,6 +21,10 @@ enum Kind {
     V_DEAD_HANDLE,     // a stream or event that is unknown or destroyed is used or destroyed
     V_BLOCK_OVERLAP,   // two workgroups of one launch write the same bytes
     V_CHECK,           // a property the scenarios assert (status, error string, getters, launch counts ...)
+    V_UNMATCHED,       // fake_rccl.cpp: a send or receive still pending when the collective is declared complete ("waits for ever")
+    V_GROUP_OPEN,      // fake_rccl.cpp: an ncclGroupStart without its ncclGroupEnd when the library call has returned
+    V_SIZE_MISMATCH,   // fake_rccl.cpp: a send met a receive of another byte count
+    V_COMM_INIT,       // fake_rccl.cpp: a second rank on one device, a repeated rank, a world other than the id's first caller's
     V_KINDS
 };
 const char *kind_name(int kind);
@@ -28,6 +32,9 @@ void violation(int kind, const std::string &what);
 uint64_t violations(int kind);  // since the last reset()
 uint64_t violations_total();
 const std::vector<std::string> &violation_log();
+// A scenario that provokes a violation on purpose (a positive test of a check): exactly `n` of `kind` must be on the books; they are
+// taken off (log lines too).  Anything else is a V_CHECK and the books stay.
+void expect_violations(int kind, uint64_t n, const std::string &why);
 
 // ---- life of the fake ----
 void reset();  // fresh books: no allocation, stream or event, clocks at zero, nothing armed, sticky error cleared
@@ -89,5 +96,32 @@ const std::vector<Op> &ops();
 bool locate(uint64_t addr, uint64_t *alloc_base, uint64_t *alloc_size);
 // Would a marker recorded NOW on `caller` be ordered behind every operation ops()[first ..]?
 bool all_before_marker(size_t first, hipStream_t caller, std::string *which);
+// the grid of the last launch whose launcher reported one (the framed plans: compared with fwt_describe)
+void note_grid(uint64_t blocks);
+uint64_t last_grid();
+
+// ---- what the simulated RCCL (fake_rccl.cpp) needs of the books ----
+int current_device();
+// A position reserved on stream `st` of the current device when a send or a receive is posted: the stream's tick and its clock.
+// false (and a violation) for a dead handle; a stream of another device than the current one is a V_CHECK.
+struct Post { int sid = -1, dev = -1; uint64_t tick = 0; std::vector<uint64_t> clock; };
+bool post(const char *who, hipStream_t st, Post *out);
+// A matched transfer.  Both ranges are checked against live allocations of the POSTING rank's device, the source must be
+// written; the transfer is ordered behind everything earlier on both streams (the two posted clocks merged) and everything later
+// on either stream is ordered behind it; hazards as for any operation; the destination is marked written.  One Op is recorded.
+void transfer(const std::string &name, const Post &src, uint64_t src_addr, const Post &dst, uint64_t dst_addr, uint64_t bytes);
+void rccl_reset();         // fake_rccl.cpp: fresh books, called by reset()
+void rccl_audit_leaks();   // fake_rccl.cpp: a V_LEAK per live communicator, called by audit_leaks()
+
+// ---- the simulated RCCL's books (fake_rccl.cpp, whose header comment has the rules) ----
+void declare_rccl();                             // its seven injectable entry points, for the coverage condition
+uint64_t rccl_calls();                           // calls of any entry point, over the whole process: proof that the fake answered
+uint64_t rccl_live();                            // communicators registered and not destroyed
+uint64_t rccl_pending();                         // sends and receives that wait for their partner
+uint64_t rccl_complete(const std::string &what); // "every rank has made this call": a V_UNMATCHED per pending operation, then dropped
+bool rccl_group_closed(const std::string &after);// a library call has returned: V_GROUP_OPEN (and the group is dropped) if one is open
+struct RcclRecord { int src_rank; uint64_t src, bytes; int dst_rank; uint64_t dst; };
+const std::vector<RcclRecord> &rccl_records();   // every matched transfer since reset() / rccl_clear_records()
+void rccl_clear_records();
 
 }  // namespace sim

@@ -1,5 +1,5 @@
 // fake_kernels.cpp -- every launcher and setup function the host layer calls (kernels.h, strided_kernels.h, fft2d_kernels.h,
-// real_kernels.h, conv_kernels.h), simulated: a launcher is an injectable call site that reports to the fake runtime
+// real_kernels.h, conv_kernels.h, stft_kernels.h), simulated: a launcher is an injectable call site that reports to the fake runtime
 // (fake_hip.h) which bytes its kernel would read and which it would write.  The regions are written out here from the
 // contract in each header's comment -- which element of which buffer a workgroup touches, as (count, stride) dimensions over a
 // contiguous piece -- and from nothing the real launchers contain: no device header is included.
@@ -7,6 +7,7 @@
 #include "../../fft_wgpu_amd/csrc/kernels.h"
 #include "../../fft_wgpu_amd/fft2d/fft2d_kernels.h"
 #include "../../fft_wgpu_amd/real/real_kernels.h"
+#include "../../fft_wgpu_amd/stft/stft_kernels.h"
 #include "../../fft_wgpu_amd/strided/strided_kernels.h"
 #include "fake_hip.h"
 
@@ -180,11 +181,11 @@ void sim::declare_launchers()
 {
     for (const char *n : {"launch_r2_stage", "launch_chunk", "launch_small32", "launch_small16", "launch_rows32", "launch_colsw", "launch_cols32",
                           "launch_p1_gen", "launch_tile", "launch_p1_1m", "launch_p2_1m", "launch_ring_1m", "launch_scale", "launch_fill",
-                          "launch_copy", "launch_spin", "launch_strided", "launch_fft2d_rows", "launch_real", "launch_conv"})
+                          "launch_copy", "launch_spin", "launch_strided", "launch_fft2d_rows", "launch_real", "launch_conv", "launch_stft"})
         sim::declare(n, sim::FN_LAUNCH);
     for (const char *n : {"setup_small32_kernels", "setup_rows32_kernels", "setup_colsw_kernels", "setup_cols32_kernels", "setup_tile_kernels",
                           "setup_1m_kernels", "setup_p1_gen_kernels", "setup_lab_1m_kernels", "setup_strided_kernels", "setup_fft2d_kernels",
-                          "setup_real_kernels", "setup_conv_kernels"})
+                          "setup_real_kernels", "setup_conv_kernels", "setup_stft_kernels"})
         sim::declare(n, sim::FN_OTHER);
 }
 
@@ -222,3 +223,24 @@ hipError_t launch_conv(uint32_t n, bool, const v2f *src, const v2f *filter, v2f 
                        {Region{dst, n * E, {{batch, n * E}}}});
 }
 }  // namespace fwc
+namespace fwt {
+hipError_t setup_stft_kernels(uint32_t) { return sim::setup("setup_stft_kernels"); }
+// The framed plans, from the prose of kernels_stft.hip and stft_geom.h and none of their functions: `src` holds `signals` signals of
+// L f32 back to back, frame f of signal s is the n floats from s L + f hop on, f < F = 1 + (L - n) / hop; frame g = s F + f is row g of
+// `dst`, n / 2 + 1 values of 8 bytes (spectrum) or 4 (power), no padding.  A workgroup owns 256 adjacent frames up to n = 64 and 16
+// from n = 128 on; the last one owns what is left.  Every workgroup reads the 4 n window bytes when there is a window.
+hipError_t launch_stft(uint32_t n, uint32_t hop, uint64_t L, uint64_t signals, bool power, const float *src, const float *window, float *dst,
+                       hipStream_t st)
+{
+    const uint64_t F = 1 + (L - n) / hop, frames = signals * F, per_wg = n <= 64 ? 256 : 16, row = (power ? 4ull : 8ull) * (n / 2 + 1);
+    const uint64_t whole = frames / per_wg, rest = frames % per_wg;
+    sim::note_grid(whole + (rest != 0));
+    std::vector<Region> rd = {Region{src, 4ull * n, {{F, 4ull * hop}, {signals, 4ull * L}}}};
+    if (window) rd.push_back(flat(window, n, 4));
+    // the rows of one workgroup, workgroup by workgroup: a stride below the length of what it steps over would be two workgroups
+    // (or two frames) on the same bytes
+    std::vector<Region> wr = {Region{dst, row, {{per_wg, row}, {whole, per_wg * row}}}};
+    if (rest) wr.push_back(Region{reinterpret_cast<const char *>(dst) + whole * per_wg * row, row, {{rest, row}}});
+    return sim::launch("launch_stft", st, rd, wr);
+}
+}  // namespace fwt
