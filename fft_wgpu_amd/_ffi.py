@@ -29,11 +29,15 @@ class FwaError(RuntimeError):
         super().__init__(f"{where}: {STATUS_NAMES.get(status, status)}: {detail}")
 
 
+# the ctypes aliases of every signature table of the package (this one and those of the side libraries' modules)
 _P = ctypes.c_void_p
 _PP = ctypes.POINTER(ctypes.c_void_p)
 _U64 = ctypes.c_uint64
 _U32 = ctypes.c_uint32
 _I32 = ctypes.c_int32
+_PI32 = ctypes.POINTER(_I32)
+_PU64 = ctypes.POINTER(_U64)
+_PI64 = ctypes.POINTER(ctypes.c_int64)
 
 _SIGNATURES = {
     "fwa_abi_version": (_I32, []),
@@ -92,6 +96,38 @@ _SIGNATURES = {
     "fwa_calib_copy": (_I32, [_P, _P, _U64, _P]),
 }
 
+
+def load(path, prefix, abi_version, signatures, header, make, remake=None, needs=None):
+    """Load one shared library of the package and bind `signatures` ({name: (restype, argtypes)}).  Raises if it was not
+    built or if its `<prefix>_abi_version()` is not `abi_version`, the version of include/`header` the table was written
+    against.  `make` is the command that builds it and `remake` the one that rebuilds it (default: the same), quoted in those
+    two messages; `needs()` loads what the library links against, once the file is known to exist."""
+    if not os.path.exists(path):
+        raise RuntimeError(
+            f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            f"or `{make}`.  fft_wgpu_amd has no CPU fallback.")
+    if needs:
+        needs()
+    L = ctypes.CDLL(path)
+    # a stale library beside newer Python (or the reverse) is refused HERE, not at the first changed signature
+    try:
+        version = getattr(L, prefix + "_abi_version")
+        version.restype = _I32
+        version.argtypes = []
+        got = int(version())
+    except AttributeError:
+        got = None
+    if got != abi_version:
+        raise RuntimeError(
+            f"{path} reports ABI version {got}, this binding was written for version {abi_version} of "
+            f"include/{header}: rebuild the library (`{remake or make}`) from the same tree")
+    for name, (res, args) in signatures.items():
+        f = getattr(L, name)  # AttributeError here = header/library mismatch
+        f.restype = res
+        f.argtypes = args
+    return L
+
+
 _libs = {}
 
 
@@ -100,27 +136,8 @@ def lib(lab=False):
     True = the laboratory build, a path = that build of the same sources (tools/build_variant.sh: A/B of compile-time defaults)."""
     path = lab if isinstance(lab, str) else (LAB_LIB_PATH if lab else LIB_PATH)
     if path not in _libs:
-        if not os.path.exists(path):
-            raise RuntimeError(
-                f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                f"or `make -C fft_wgpu_amd/csrc{' lab' if lab is True else ''}`.  fft_wgpu_amd has no CPU fallback.")
-        L = ctypes.CDLL(path)
-        # a stale library beside newer Python (or the reverse) is refused HERE, not at the first changed signature
-        try:
-            L.fwa_abi_version.restype = _I32
-            L.fwa_abi_version.argtypes = []
-            got = int(L.fwa_abi_version())
-        except AttributeError:
-            got = None
-        if got != ABI_VERSION:
-            raise RuntimeError(
-                f"{path} reports ABI version {got}, this binding was written for version {ABI_VERSION} of "
-                f"include/fft_wgpu_amd.h: rebuild the library (`make -C fft_wgpu_amd/csrc all lab`) from the same tree")
-        for name, (res, args) in _SIGNATURES.items():
-            f = getattr(L, name)  # AttributeError here = header/library mismatch
-            f.restype = res
-            f.argtypes = args
-        _libs[path] = L
+        _libs[path] = load(path, "fwa", ABI_VERSION, _SIGNATURES, "fft_wgpu_amd.h",
+                           f"make -C fft_wgpu_amd/csrc{' lab' if lab is True else ''}", "make -C fft_wgpu_amd/csrc all lab")
     return _libs[path]
 
 

@@ -5,10 +5,9 @@
 // the device.
 #include "../../include/fft_wgpu_amd_conv.h"
 
-#include <cstring>
 #include <new>
 
-#include "../csrc/internal.h"
+#include "../side/side_host.h"
 #include "conv_kernels.h"
 
 using fwa_int::fail;
@@ -36,22 +35,7 @@ int32_t check_shape(const fwa_ctx *ctx, uint32_t n, uint64_t batch, fwc::Geometr
     if (batch > (~0ull) / (8ull * n)) return fail(ctx, FWA_ERR_INVALID_ARG, "8 * fft_len * batch overflows 64 bits");
     *g = fwc::geometry(n);
     *blocks = fwc::blocks(*g, batch);
-    if (*blocks > 0x7fffffffull)
-        return fail(ctx, FWA_ERR_UNSUPPORTED, "the shape needs more than 2^31 - 1 workgroups in one launch");
-    return FWA_OK;
-}
-
-int32_t check_buf(const fwa_ctx *ctx, const fwa_buf *b, const char *name)
-{
-    if (!b->ctx) return fail(ctx, FWA_ERR_INVALID_ARG, std::string(name) + " belongs to a context that has been destroyed");
-    if (b->ctx != ctx) return fail(ctx, FWA_ERR_INVALID_ARG, std::string(name) + " belongs to another context");
-    return FWA_OK;  // every fwa_buf is 16-byte aligned: fwa_buf_alloc hands out allocation bases, fwa_buf_wrap refuses any other pointer
-}
-
-bool overlap(const fwa_buf *a, const fwa_buf *b)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a->p), b0 = reinterpret_cast<uintptr_t>(b->p);
-    return a0 < b0 + b->bytes && b0 < a0 + a->bytes;
+    return side::check_grid(ctx, *blocks);
 }
 
 }  // namespace
@@ -78,9 +62,9 @@ int32_t fwc_plan_create(fwa_ctx *ctx, int32_t kind, uint32_t flags, uint32_t n, 
     if (!out) return fail(ctx, FWA_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     if (!ctx || !src || !filter || !dst) return fail(ctx, FWA_ERR_INVALID_ARG, "ctx/src/filter/dst is NULL");
-    if (int32_t st = check_buf(ctx, src, "src")) return st;
-    if (int32_t st = check_buf(ctx, filter, "filter")) return st;
-    if (int32_t st = check_buf(ctx, dst, "dst")) return st;
+    if (int32_t st = side::check_owner(ctx, src, "src")) return st;
+    if (int32_t st = side::check_owner(ctx, filter, "filter")) return st;
+    if (int32_t st = side::check_owner(ctx, dst, "dst")) return st;
     if (kind != FWA_INVERSE_SCALED && kind != FWA_INVERSE_UNSCALED)
         return fail(ctx, FWA_ERR_INVALID_ARG, "convolution plans are FWA_INVERSE_SCALED or FWA_INVERSE_UNSCALED");
     if (flags & ~(uint32_t)FWC_CONJ_FILTER) return fail(ctx, FWA_ERR_INVALID_ARG, "unknown flag bits: " + std::to_string(flags));
@@ -95,9 +79,9 @@ int32_t fwc_plan_create(fwa_ctx *ctx, int32_t kind, uint32_t flags, uint32_t n, 
     if (src->bytes != dst->bytes)
         return fail(ctx, FWA_ERR_INVALID_ARG, "src and dst disagree about batch: " + std::to_string(src->bytes / row) + " and " +
                     std::to_string(dst->bytes / row) + " rows");
-    if (src != dst && overlap(src, dst))
+    if (src != dst && side::overlap(src, dst))
         return fail(ctx, FWA_ERR_INVALID_ARG, "src and dst overlap without being the same buffer: in place means dst == src");
-    if (overlap(filter, dst)) return fail(ctx, FWA_ERR_INVALID_ARG, "filter and dst overlap: the filter is never written");
+    if (side::overlap(filter, dst)) return fail(ctx, FWA_ERR_INVALID_ARG, "filter and dst overlap: the filter is never written");
     const uint64_t batch = src->bytes / row;
     if (int32_t st = check_shape(ctx, n, batch, &g, &blocks)) return st;
 
@@ -115,10 +99,7 @@ int32_t fwc_plan_exec(fwc_plan *plan, fwa_stream *stream)
 {
     if (!plan) return fail(nullptr, FWA_ERR_INVALID_ARG, "plan is NULL");
     fwa_ctx *ctx = plan->ctx;
-    if (stream) {
-        if (!stream->ctx) return fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to a context that has been destroyed");
-        if (stream->ctx != ctx) return fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to another context");
-    }
+    if (int32_t st = side::check_stream(ctx, stream)) return st;
     USE_DEVICE(ctx);
     const float scale = plan->kind == FWA_INVERSE_SCALED ? 1.0f / (float)plan->n : 1.0f;  // an exact power of two
     const hipError_t e = fwc::launch_conv(plan->n, (plan->flags & FWC_CONJ_FILTER) != 0, static_cast<const v2f *>(plan->src->p),
@@ -130,19 +111,13 @@ int32_t fwc_plan_exec(fwc_plan *plan, fwa_stream *stream)
 
 int32_t fwc_plan_get_i64(const fwc_plan *plan, const char *key, int64_t *value)
 {
-    if (!plan || !key || !value) return fail(plan ? plan->ctx : nullptr, FWA_ERR_INVALID_ARG, "plan/key/value is NULL");
-    const struct { const char *key; int64_t v; } keys[] = {
+    if (int32_t st = side::check_get(plan, key, value)) return st;
+    return side::get_i64(plan->ctx, key, value, {
         {"fft_len", (int64_t)plan->n}, {"batch", (int64_t)plan->batch}, {"filters", (int64_t)plan->filters},
         {"in_place", plan->src == plan->dst ? 1 : 0}, {"launches_per_exec", 1},
         {"threads", plan->geom.threads}, {"lds_bytes", plan->geom.lds_bytes}, {"rows_per_block", plan->geom.rows_per_block},
         {"blocks", (int64_t)plan->blocks},
-    };
-    for (const auto &k : keys)
-        if (!std::strcmp(key, k.key)) {
-            *value = k.v;
-            return FWA_OK;
-        }
-    return fail(plan->ctx, FWA_ERR_INVALID_ARG, std::string("unknown key: ") + key);
+    });
 }
 
 int32_t fwc_plan_destroy(fwc_plan *plan)

@@ -11,26 +11,20 @@ package is imported, and there is no fallback: a missing library or a failing ca
 import ctypes
 import os
 
-from . import _ffi
+from . import _ffi, _side
+from ._ffi import _I32, _P, _PI32, _PI64, _PP, _PU64, _U32, _U64
 from . import strided as _strided
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfft_wgpu_amd_2d.so")
 ABI_VERSION = 1   # FW2_ABI_VERSION of the include/fft_wgpu_amd_2d.h this binding was written against
 
-_P = ctypes.c_void_p
-_PP = ctypes.POINTER(ctypes.c_void_p)
-_U64 = ctypes.c_uint64
-_U32 = ctypes.c_uint32
-_I32 = ctypes.c_int32
-_PI32 = ctypes.POINTER(_I32)
-
 _SIGNATURES = {
     "fw2_abi_version": (_I32, []),
-    "fw2_describe": (_I32, [_U32, _U32, _U64, _PI32, _PI32, _PI32, ctypes.POINTER(_U64)]),
+    "fw2_describe": (_I32, [_U32, _U32, _U64, _PI32, _PI32, _PI32, _PU64]),
     "fw2_plan_create": (_I32, [_P, _I32, _U32, _U32, _P, _PP]),
     "fw2_plan_exec": (_I32, [_P, _P]),
-    "fw2_plan_get_i64": (_I32, [_P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
+    "fw2_plan_get_i64": (_I32, [_P, ctypes.c_char_p, _PI64]),
     "fw2_plan_destroy": (_I32, [_P]),
 }
 
@@ -38,30 +32,12 @@ _lib = None
 
 
 def lib():
-    """Load libfft_wgpu_amd_2d.so (once).  Raises if it was not built or reports another ABI version."""
+    """Load libfft_wgpu_amd_2d.so (once), after the column plans and the main library, which it links against.  Raises if it
+    was not built or reports another ABI version."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` or "
-                f"`make -C fft_wgpu_amd/fft2d`.  fft_wgpu_amd has no CPU fallback.")
-        _strided.lib()  # the libraries it links against first: the main one (contexts, buffers) and the column plans
-        L = ctypes.CDLL(LIB_PATH)
-        try:
-            L.fw2_abi_version.restype = _I32
-            L.fw2_abi_version.argtypes = []
-            got = int(L.fw2_abi_version())
-        except AttributeError:
-            got = None
-        if got != ABI_VERSION:
-            raise RuntimeError(
-                f"{LIB_PATH} reports ABI version {got}, this binding was written for version {ABI_VERSION} of "
-                f"include/fft_wgpu_amd_2d.h: rebuild the library (`make -C fft_wgpu_amd/fft2d`) from the same tree")
-        for name, (res, args) in _SIGNATURES.items():
-            f = getattr(L, name)  # AttributeError here = header/library mismatch
-            f.restype = res
-            f.argtypes = args
-        _lib = L
+        _lib = _ffi.load(LIB_PATH, "fw2", ABI_VERSION, _SIGNATURES, "fft_wgpu_amd_2d.h", "make -C fft_wgpu_amd/fft2d",
+                         needs=_strided.lib)
     return _lib
 
 
@@ -74,47 +50,15 @@ def describe(rows, cols, batch=1):
     return {"launches": launches.value, "row_threads": threads.value, "row_lds_bytes": lds.value, "row_blocks": blocks.value}
 
 
-class _Plan:
+class _Plan(_side.Plan):
+    _prefix = "fw2"
     _kind = None
 
     def __init__(self, device, queue, src, rows, cols):
-        self.device = device
-        self.queue = queue          # kept for signature parity with the contiguous plans; unused
         self.src = src
         self.rows = rows
         self.cols = cols
-        self._S = lib()
-        h = ctypes.c_void_p()
-        st = self._S.fw2_plan_create(device._h, self._kind, rows, cols, src._h, ctypes.byref(h))
-        _ffi.check(st, device._h, f"fw2_plan_create({type(self).__name__})", device._L)
-        self._h = h
-
-    @classmethod
-    def new(cls, *args):
-        return cls(*args)
-
-    def proc(self, encoder):
-        """Enqueue the transform on ``encoder``; the result is in ``src``, which is returned."""
-        st = self._S.fw2_plan_exec(self._h, encoder._h if encoder is not None else None)
-        _ffi.check(st, self.device._h, "fw2_plan_exec", self.device._L)
-        return self.src
-
-    def get(self, key):
-        v = ctypes.c_int64()
-        _ffi.check(self._S.fw2_plan_get_i64(self._h, key.encode(), ctypes.byref(v)), self.device._h, "fw2_plan_get_i64",
-                   self.device._L)
-        return v.value
-
-    def destroy(self):
-        if self._h:
-            self._S.fw2_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        self._create(lib(), device, queue, src, device._h, self._kind, rows, cols, src._h)
 
 
 class Forward(_Plan):

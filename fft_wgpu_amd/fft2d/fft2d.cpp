@@ -4,10 +4,9 @@
 // exec allocates nothing and destroy frees nothing on the device.
 #include "../../include/fft_wgpu_amd_2d.h"
 
-#include <cstring>
 #include <new>
 
-#include "../csrc/internal.h"
+#include "../side/side_host.h"
 #include "fft2d_kernels.h"
 
 using fwa_int::fail;
@@ -44,9 +43,7 @@ int32_t check_shape(const fwa_ctx *ctx, uint32_t rows, uint32_t cols, uint64_t b
     if (batch > (~0ull) / (8ull * rows * cols)) return fail(ctx, FWA_ERR_INVALID_ARG, "8 * rows * cols * batch overflows 64 bits");
     *g = fw2::geometry(rows, cols);
     *row_blocks = fw2::row_blocks(*g, batch * rows, cols);
-    if (*row_blocks > 0x7fffffffull)
-        return fail(ctx, FWA_ERR_UNSUPPORTED, "the shape needs more than 2^31 - 1 workgroups in one launch");
-    return FWA_OK;
+    return side::check_grid(ctx, *row_blocks);
 }
 
 }  // namespace
@@ -75,10 +72,8 @@ int32_t fw2_plan_create(fwa_ctx *ctx, int32_t kind, uint32_t rows, uint32_t cols
     if (!out) return fail(ctx, FWA_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     if (!ctx || !buf) return fail(ctx, FWA_ERR_INVALID_ARG, "ctx/buf is NULL");
-    if (!buf->ctx) return fail(ctx, FWA_ERR_INVALID_ARG, "the buffer belongs to a context that has been destroyed");
-    if (buf->ctx != ctx) return fail(ctx, FWA_ERR_INVALID_ARG, "the buffer belongs to another context");
-    if (kind != FWA_FORWARD && kind != FWA_INVERSE_SCALED && kind != FWA_INVERSE_UNSCALED)
-        return fail(ctx, FWA_ERR_INVALID_ARG, "2-D plans are FWA_FORWARD, FWA_INVERSE_SCALED or FWA_INVERSE_UNSCALED");
+    if (int32_t st = side::check_owner(ctx, buf, "the buffer")) return st;
+    if (int32_t st = side::check_kind(ctx, kind, "2-D plans")) return st;
     fw2::Geometry g;
     uint64_t blocks = 0;
     if (int32_t st = check_shape(ctx, rows, cols, 0, &g, &blocks)) return st;
@@ -114,10 +109,7 @@ int32_t fw2_plan_exec(fw2_plan *plan, fwa_stream *stream)
 {
     if (!plan) return fail(nullptr, FWA_ERR_INVALID_ARG, "plan is NULL");
     fwa_ctx *ctx = plan->ctx;
-    if (stream) {
-        if (!stream->ctx) return fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to a context that has been destroyed");
-        if (stream->ctx != ctx) return fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to another context");
-    }
+    if (int32_t st = side::check_stream(ctx, stream)) return st;
     USE_DEVICE(ctx);
     const int dir = plan->kind == FWA_FORWARD ? fwa::FWD : fwa::INV;
     const bool scaled = plan->kind == FWA_INVERSE_SCALED;  // 1 / cols here, 1 / rows in the column pass: exact powers of two
@@ -130,19 +122,13 @@ int32_t fw2_plan_exec(fw2_plan *plan, fwa_stream *stream)
 
 int32_t fw2_plan_get_i64(const fw2_plan *plan, const char *key, int64_t *value)
 {
-    if (!plan || !key || !value) return fail(plan ? plan->ctx : nullptr, FWA_ERR_INVALID_ARG, "plan/key/value is NULL");
-    const struct { const char *key; int64_t v; } keys[] = {
+    if (int32_t st = side::check_get(plan, key, value)) return st;
+    return side::get_i64(plan->ctx, key, value, {
         {"rows", (int64_t)plan->rows}, {"cols", (int64_t)plan->cols}, {"batch", (int64_t)plan->batch},
         {"launches_per_exec", plan->geom.launches}, {"row_threads", plan->geom.row_threads},
         {"row_lds_bytes", plan->geom.row_lds_bytes}, {"row_blocks", (int64_t)plan->row_blocks},
         {"col_blocks", (int64_t)plan->col_blocks},
-    };
-    for (const auto &k : keys)
-        if (!std::strcmp(key, k.key)) {
-            *value = k.v;
-            return FWA_OK;
-        }
-    return fail(plan->ctx, FWA_ERR_INVALID_ARG, std::string("unknown key: ") + key);
+    });
 }
 
 int32_t fw2_plan_destroy(fw2_plan *plan)

@@ -5,10 +5,9 @@
 // the device.
 #include "../../include/fft_wgpu_amd_real.h"
 
-#include <cstring>
 #include <new>
 
-#include "../csrc/internal.h"
+#include "../side/side_host.h"
 #include "real_kernels.h"
 
 using fwa_int::fail;
@@ -36,16 +35,7 @@ int32_t check_shape(const fwa_ctx *ctx, uint32_t n, uint64_t batch, fwr::Geometr
     if (batch > (~0ull) / (4ull * (n + 2))) return fail(ctx, FWA_ERR_INVALID_ARG, "8 * (fft_len / 2 + 1) * batch overflows 64 bits");
     *g = fwr::geometry(n);
     *blocks = fwr::blocks(*g, batch);
-    if (*blocks > 0x7fffffffull)
-        return fail(ctx, FWA_ERR_UNSUPPORTED, "the shape needs more than 2^31 - 1 workgroups in one launch");
-    return FWA_OK;
-}
-
-int32_t check_buf(const fwa_ctx *ctx, const fwa_buf *b, const char *name)
-{
-    if (!b->ctx) return fail(ctx, FWA_ERR_INVALID_ARG, std::string(name) + " belongs to a context that has been destroyed");
-    if (b->ctx != ctx) return fail(ctx, FWA_ERR_INVALID_ARG, std::string(name) + " belongs to another context");
-    return FWA_OK;
+    return side::check_grid(ctx, *blocks);
 }
 
 }  // namespace
@@ -71,13 +61,10 @@ int32_t fwr_plan_create(fwa_ctx *ctx, int32_t kind, uint32_t n, fwa_buf *src, fw
     if (!out) return fail(ctx, FWA_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     if (!ctx || !src || !dst) return fail(ctx, FWA_ERR_INVALID_ARG, "ctx/src/dst is NULL");
-    if (int32_t st = check_buf(ctx, src, "src")) return st;
-    if (int32_t st = check_buf(ctx, dst, "dst")) return st;
-    if (kind != FWA_FORWARD && kind != FWA_INVERSE_SCALED && kind != FWA_INVERSE_UNSCALED)
-        return fail(ctx, FWA_ERR_INVALID_ARG, "real plans are FWA_FORWARD, FWA_INVERSE_SCALED or FWA_INVERSE_UNSCALED");
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src->p), d0 = reinterpret_cast<uintptr_t>(dst->p);
-    if (s0 < d0 + dst->bytes && d0 < s0 + src->bytes)
-        return fail(ctx, FWA_ERR_INVALID_ARG, "src and dst overlap: real plans are out of place");
+    if (int32_t st = side::check_owner(ctx, src, "src")) return st;
+    if (int32_t st = side::check_owner(ctx, dst, "dst")) return st;
+    if (int32_t st = side::check_kind(ctx, kind, "real plans")) return st;
+    if (side::overlap(src, dst)) return fail(ctx, FWA_ERR_INVALID_ARG, "src and dst overlap: real plans are out of place");
     fwr::Geometry g;
     uint64_t blocks = 0;
     if (int32_t st = check_shape(ctx, n, 0, &g, &blocks)) return st;
@@ -106,10 +93,7 @@ int32_t fwr_plan_exec(fwr_plan *plan, fwa_stream *stream)
 {
     if (!plan) return fail(nullptr, FWA_ERR_INVALID_ARG, "plan is NULL");
     fwa_ctx *ctx = plan->ctx;
-    if (stream) {
-        if (!stream->ctx) return fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to a context that has been destroyed");
-        if (stream->ctx != ctx) return fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to another context");
-    }
+    if (int32_t st = side::check_stream(ctx, stream)) return st;
     USE_DEVICE(ctx);
     const int dir = plan->kind == FWA_FORWARD ? fwa::FWD : fwa::INV;
     const float scale = plan->kind == FWA_INVERSE_SCALED ? 1.0f / (float)plan->n : 1.0f;  // an exact power of two
@@ -121,18 +105,12 @@ int32_t fwr_plan_exec(fwr_plan *plan, fwa_stream *stream)
 
 int32_t fwr_plan_get_i64(const fwr_plan *plan, const char *key, int64_t *value)
 {
-    if (!plan || !key || !value) return fail(plan ? plan->ctx : nullptr, FWA_ERR_INVALID_ARG, "plan/key/value is NULL");
-    const struct { const char *key; int64_t v; } keys[] = {
+    if (int32_t st = side::check_get(plan, key, value)) return st;
+    return side::get_i64(plan->ctx, key, value, {
         {"fft_len", (int64_t)plan->n}, {"batch", (int64_t)plan->batch}, {"launches_per_exec", 1},
         {"threads", plan->geom.threads}, {"lds_bytes", plan->geom.lds_bytes}, {"rows_per_block", plan->geom.rows_per_block},
         {"blocks", (int64_t)plan->blocks},
-    };
-    for (const auto &k : keys)
-        if (!std::strcmp(key, k.key)) {
-            *value = k.v;
-            return FWA_OK;
-        }
-    return fail(plan->ctx, FWA_ERR_INVALID_ARG, std::string("unknown key: ") + key);
+    });
 }
 
 int32_t fwr_plan_destroy(fwr_plan *plan)

@@ -5,10 +5,9 @@
 // allocates nothing and destroy frees nothing on the device.
 #include "../../include/fft_wgpu_amd_stft.h"
 
-#include <cstring>
 #include <new>
 
-#include "../csrc/internal.h"
+#include "../side/side_host.h"
 #include "stft_kernels.h"
 
 using fwa_int::fail;
@@ -44,22 +43,7 @@ int32_t check_shape(const fwa_ctx *ctx, uint32_t n, uint32_t hop, uint64_t L, ui
         return fail(ctx, FWA_ERR_INVALID_ARG, "8 * (fft_len / 2 + 1) * frames overflows 64 bits");
     *g = fwt::geometry(n);
     *blocks = fwt::blocks(*g, signals * *per_signal);
-    if (*blocks > 0x7fffffffull)
-        return fail(ctx, FWA_ERR_UNSUPPORTED, "the shape needs more than 2^31 - 1 workgroups in one launch");
-    return FWA_OK;
-}
-
-int32_t check_buf(const fwa_ctx *ctx, const fwa_buf *b, const char *name)
-{
-    if (!b->ctx) return fail(ctx, FWA_ERR_INVALID_ARG, std::string(name) + " belongs to a context that has been destroyed");
-    if (b->ctx != ctx) return fail(ctx, FWA_ERR_INVALID_ARG, std::string(name) + " belongs to another context");
-    return FWA_OK;  // every fwa_buf is 16-byte aligned: fwa_buf_alloc hands out allocation bases, fwa_buf_wrap refuses any other pointer
-}
-
-bool overlap(const fwa_buf *a, const fwa_buf *b)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a->p), b0 = reinterpret_cast<uintptr_t>(b->p);
-    return a0 < b0 + b->bytes && b0 < a0 + a->bytes;
+    return side::check_grid(ctx, *blocks);
 }
 
 }  // namespace
@@ -88,16 +72,16 @@ int32_t fwt_plan_create(fwa_ctx *ctx, int32_t output, uint32_t n, uint32_t hop, 
     if (!out) return fail(ctx, FWA_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     if (!ctx || !src || !dst) return fail(ctx, FWA_ERR_INVALID_ARG, "ctx/src/dst is NULL");
-    if (int32_t st = check_buf(ctx, src, "src")) return st;
+    if (int32_t st = side::check_owner(ctx, src, "src")) return st;
     if (window)
-        if (int32_t st = check_buf(ctx, window, "window")) return st;
-    if (int32_t st = check_buf(ctx, dst, "dst")) return st;
+        if (int32_t st = side::check_owner(ctx, window, "window")) return st;
+    if (int32_t st = side::check_owner(ctx, dst, "dst")) return st;
     if (output != FWT_SPECTRUM && output != FWT_POWER) return fail(ctx, FWA_ERR_INVALID_ARG, "output is FWT_SPECTRUM or FWT_POWER");
     fwt::Geometry g;
     uint64_t per_signal = 0, blocks = 0;
     if (int32_t st = check_shape(ctx, n, hop, signal_len, 0, &g, &per_signal, &blocks)) return st;
-    if (overlap(src, dst)) return fail(ctx, FWA_ERR_INVALID_ARG, "src and dst overlap: framed plans are out of place");
-    if (window && overlap(window, dst)) return fail(ctx, FWA_ERR_INVALID_ARG, "window and dst overlap: the window is never written");
+    if (side::overlap(src, dst)) return fail(ctx, FWA_ERR_INVALID_ARG, "src and dst overlap: framed plans are out of place");
+    if (window && side::overlap(window, dst)) return fail(ctx, FWA_ERR_INVALID_ARG, "window and dst overlap: the window is never written");
     if (window && window->bytes != 4ull * n)
         return fail(ctx, FWA_ERR_INVALID_ARG, "the window holds " + std::to_string(window->bytes) + " bytes, not 4 * fft_len = " +
                     std::to_string(4ull * n));
@@ -125,10 +109,7 @@ int32_t fwt_plan_exec(fwt_plan *plan, fwa_stream *stream)
 {
     if (!plan) return fail(nullptr, FWA_ERR_INVALID_ARG, "plan is NULL");
     fwa_ctx *ctx = plan->ctx;
-    if (stream) {
-        if (!stream->ctx) return fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to a context that has been destroyed");
-        if (stream->ctx != ctx) return fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to another context");
-    }
+    if (int32_t st = side::check_stream(ctx, stream)) return st;
     USE_DEVICE(ctx);
     const hipError_t e = fwt::launch_stft(plan->n, plan->hop, plan->sig_len, plan->signals, plan->output == FWT_POWER,
                                           static_cast<const float *>(plan->src->p),
@@ -140,20 +121,14 @@ int32_t fwt_plan_exec(fwt_plan *plan, fwa_stream *stream)
 
 int32_t fwt_plan_get_i64(const fwt_plan *plan, const char *key, int64_t *value)
 {
-    if (!plan || !key || !value) return fail(plan ? plan->ctx : nullptr, FWA_ERR_INVALID_ARG, "plan/key/value is NULL");
-    const struct { const char *key; int64_t v; } keys[] = {
+    if (int32_t st = side::check_get(plan, key, value)) return st;
+    return side::get_i64(plan->ctx, key, value, {
         {"fft_len", (int64_t)plan->n}, {"hop", (int64_t)plan->hop}, {"signal_len", (int64_t)plan->sig_len},
         {"signals", (int64_t)plan->signals}, {"frames_per_signal", (int64_t)plan->per_signal},
         {"frames", (int64_t)(plan->signals * plan->per_signal)}, {"output", plan->output}, {"windowed", plan->window ? 1 : 0},
         {"launches_per_exec", 1}, {"threads", plan->geom.threads}, {"lds_bytes", plan->geom.lds_bytes},
         {"frames_per_block", plan->geom.rows_per_block}, {"blocks", (int64_t)plan->blocks},
-    };
-    for (const auto &k : keys)
-        if (!std::strcmp(key, k.key)) {
-            *value = k.v;
-            return FWA_OK;
-        }
-    return fail(plan->ctx, FWA_ERR_INVALID_ARG, std::string("unknown key: ") + key);
+    });
 }
 
 int32_t fwt_plan_destroy(fwt_plan *plan)

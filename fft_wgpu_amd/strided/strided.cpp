@@ -5,10 +5,9 @@
 // nothing on the device.
 #include "../../include/fft_wgpu_amd_strided.h"
 
-#include <cstring>
 #include <new>
 
-#include "../csrc/internal.h"
+#include "../side/side_host.h"
 #include "strided_kernels.h"
 
 using fwa_int::fail;
@@ -35,8 +34,7 @@ int32_t check_shape(const fwa_ctx *ctx, uint32_t fft_len, uint64_t howmany, uint
     if (howmany > (~0ull) / (8ull * fft_len)) return fail(ctx, FWA_ERR_INVALID_ARG, "8 * fft_len * howmany overflows 64 bits");
     *g = fws::geometry(fft_len);
     const uint64_t wgs = fws::wgs_per_matrix(*g, howmany);
-    if (batch > 0x7fffffffull / wgs)
-        return fail(ctx, FWA_ERR_UNSUPPORTED, "the shape needs more than 2^31 - 1 workgroups in one launch");
+    if (int32_t st = side::check_grid(ctx, batch, wgs)) return st;
     *blocks = batch * wgs;
     return FWA_OK;
 }
@@ -65,11 +63,8 @@ int32_t fws_plan_create(fwa_ctx *ctx, int32_t kind, uint32_t fft_len, uint64_t h
     if (!out) return fail(ctx, FWA_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     if (!ctx || !buf) return fail(ctx, FWA_ERR_INVALID_ARG, "ctx/buf is NULL");
-    // (LIVE_HANDLE's rule, with the message on the context the caller reads it from)
-    if (!buf->ctx) return fail(ctx, FWA_ERR_INVALID_ARG, "the buffer belongs to a context that has been destroyed");
-    if (buf->ctx != ctx) return fail(ctx, FWA_ERR_INVALID_ARG, "the buffer belongs to another context");
-    if (kind != FWA_FORWARD && kind != FWA_INVERSE_SCALED && kind != FWA_INVERSE_UNSCALED)
-        return fail(ctx, FWA_ERR_INVALID_ARG, "strided plans are FWA_FORWARD, FWA_INVERSE_SCALED or FWA_INVERSE_UNSCALED");
+    if (int32_t st = side::check_owner(ctx, buf, "the buffer")) return st;
+    if (int32_t st = side::check_kind(ctx, kind, "strided plans")) return st;
     fws::Geometry g;
     uint64_t blocks = 0;
     if (int32_t st = check_shape(ctx, fft_len, howmany, 0, &g, &blocks)) return st;
@@ -94,10 +89,7 @@ int32_t fws_plan_exec(fws_plan *plan, fwa_stream *stream)
 {
     if (!plan) return fail(nullptr, FWA_ERR_INVALID_ARG, "plan is NULL");
     fwa_ctx *ctx = plan->ctx;
-    if (stream) {
-        if (!stream->ctx) return fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to a context that has been destroyed");
-        if (stream->ctx != ctx) return fail(ctx, FWA_ERR_INVALID_ARG, "the stream belongs to another context");
-    }
+    if (int32_t st = side::check_stream(ctx, stream)) return st;
     USE_DEVICE(ctx);
     const int dir = plan->kind == FWA_FORWARD ? fwa::FWD : fwa::INV;
     const float scale = plan->kind == FWA_INVERSE_SCALED ? 1.0f / (float)plan->n : 1.0f;  // an exact power of two
@@ -109,18 +101,12 @@ int32_t fws_plan_exec(fws_plan *plan, fwa_stream *stream)
 
 int32_t fws_plan_get_i64(const fws_plan *plan, const char *key, int64_t *value)
 {
-    if (!plan || !key || !value) return fail(plan ? plan->ctx : nullptr, FWA_ERR_INVALID_ARG, "plan/key/value is NULL");
-    const struct { const char *key; int64_t v; } keys[] = {
+    if (int32_t st = side::check_get(plan, key, value)) return st;
+    return side::get_i64(plan->ctx, key, value, {
         {"fft_len", (int64_t)plan->n}, {"howmany", (int64_t)plan->howmany}, {"batch", (int64_t)plan->batch},
         {"tile_cols", plan->geom.tile_cols}, {"threads", plan->geom.threads}, {"lds_bytes", plan->geom.lds_bytes},
         {"blocks", (int64_t)plan->blocks}, {"launches_per_exec", 1},
-    };
-    for (const auto &k : keys)
-        if (!std::strcmp(key, k.key)) {
-            *value = k.v;
-            return FWA_OK;
-        }
-    return fail(plan->ctx, FWA_ERR_INVALID_ARG, std::string("unknown key: ") + key);
+    });
 }
 
 int32_t fws_plan_destroy(fws_plan *plan)

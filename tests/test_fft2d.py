@@ -9,6 +9,7 @@ import re
 import subprocess
 
 import pytest
+import side_libs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "fft_wgpu_amd_2d.h")
@@ -20,10 +21,7 @@ NAMES = ["fw2_abi_version", "fw2_describe", "fw2_plan_create", "fw2_plan_destroy
 @pytest.fixture(scope="session")
 def fft2d():
     """The library is built by the session that needs it (tests/conftest.py builds csrc only)."""
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "fft_wgpu_amd", "fft2d")])
-    from fft_wgpu_amd import fft2d as m
-    m.lib()
-    return m
+    return side_libs.load("fft2d")
 
 
 @pytest.fixture(scope="session")

@@ -15,7 +15,6 @@ rows, and 1.  F = 3 divides no tile: the filter row wraps inside a workgroup.
 import ctypes
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -25,6 +24,7 @@ import conv_cases as cc
 import guarded_arena as ga
 import side_sweeps as ss
 from oracle.device_run import open_gpu
+import side_libs
 
 pytestmark = pytest.mark.gpu
 
@@ -35,10 +35,7 @@ SPECIAL = [32, 64, 2048]
 
 @pytest.fixture(scope="module")
 def conv():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "fft_wgpu_amd", "conv")])
-    from fft_wgpu_amd import conv as m
-    m.lib()
-    return m
+    return side_libs.load("conv")
 
 
 @pytest.fixture(scope="module")

@@ -17,7 +17,6 @@ figures there (tests/golden/fft2d_error.json is such a record; no test pins to i
 import ctypes
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -28,6 +27,7 @@ import side_sweeps as ss
 from conftest import REL_TOL
 from oracle import error_budget as eb
 from oracle.device_run import open_gpu
+import side_libs
 
 pytestmark = pytest.mark.gpu
 
@@ -54,10 +54,7 @@ def default_batch(rows, cols):
 
 @pytest.fixture(scope="session")
 def fft2d():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "fft_wgpu_amd", "fft2d")])
-    from fft_wgpu_amd import fft2d as m
-    m.lib()
-    return m
+    return side_libs.load("fft2d")
 
 
 @pytest.fixture(scope="module")

@@ -21,7 +21,6 @@ figures there (tests/golden/real_error.json is such a record; no test pins to it
 import ctypes
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -32,6 +31,7 @@ import side_sweeps as ss
 from conftest import REL_TOL
 from oracle import error_budget as eb
 from oracle.device_run import open_gpu
+import side_libs
 
 pytestmark = pytest.mark.gpu
 
@@ -51,10 +51,7 @@ def default_batch(n):
 
 @pytest.fixture(scope="session")
 def real():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "fft_wgpu_amd", "real")])
-    from fft_wgpu_amd import real as m
-    m.lib()
-    return m
+    return side_libs.load("real")
 
 
 @pytest.fixture(scope="module")

@@ -10,7 +10,6 @@ figures there (tests/golden/stft_error.json is such a record; no test pins to it
 import ctypes
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,6 +19,7 @@ import guarded_arena as ga
 import side_sweeps as ss
 import stft_cases as sc
 from oracle.device_run import open_gpu
+import side_libs
 
 pytestmark = pytest.mark.gpu
 
@@ -29,18 +29,12 @@ INVALID_ARG, UNSUPPORTED = 1, 6
 
 @pytest.fixture(scope="session")
 def stft():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "fft_wgpu_amd", "stft")])
-    from fft_wgpu_amd import stft as m
-    m.lib()
-    return m
+    return side_libs.load("stft")
 
 
 @pytest.fixture(scope="session")
 def real():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "fft_wgpu_amd", "real")])
-    from fft_wgpu_amd import real as m
-    m.lib()
-    return m
+    return side_libs.load("real")
 
 
 @pytest.fixture(scope="module")

@@ -14,7 +14,6 @@ figures there (tests/golden/strided_error.json is such a record; no test pins to
 import ctypes
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -25,6 +24,7 @@ import side_sweeps as ss
 from conftest import REL_TOL
 from oracle import error_budget as eb
 from oracle.device_run import open_gpu
+import side_libs
 
 pytestmark = pytest.mark.gpu
 
@@ -36,10 +36,7 @@ INVALID_ARG, UNSUPPORTED = 1, 6
 
 @pytest.fixture(scope="session")
 def strided():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "fft_wgpu_amd", "strided")])
-    from fft_wgpu_amd import strided as s
-    s.lib()
-    return s
+    return side_libs.load("strided")
 
 
 @pytest.fixture(scope="module")

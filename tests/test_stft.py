@@ -18,6 +18,7 @@ import pytest
 
 import stft_cases as sc
 from conftest import GOLDEN
+import side_libs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "fft_wgpu_amd_stft.h")
@@ -29,18 +30,12 @@ NAMES = ["fwt_abi_version", "fwt_describe", "fwt_plan_create", "fwt_plan_destroy
 @pytest.fixture(scope="session")
 def stft():
     """The library is built by the session that needs it (tests/conftest.py builds csrc only)."""
-    subprocess.check_call(["make", "-s", "-C", STFT_DIR])
-    from fft_wgpu_amd import stft as m
-    m.lib()
-    return m
+    return side_libs.load("stft")
 
 
 @pytest.fixture(scope="session")
 def real():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "fft_wgpu_amd", "real")])
-    from fft_wgpu_amd import real as m
-    m.lib()
-    return m
+    return side_libs.load("real")
 
 
 # ---- ABI ------------------------------------------------------------------------------------------------------------

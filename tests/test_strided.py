@@ -9,6 +9,7 @@ import re
 import subprocess
 
 import pytest
+import side_libs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "fft_wgpu_amd_strided.h")
@@ -19,10 +20,7 @@ INVALID_ARG, UNSUPPORTED = 1, 6
 @pytest.fixture(scope="session")
 def strided():
     """The library is built by the session that needs it (tests/conftest.py builds csrc only)."""
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "fft_wgpu_amd", "strided")])
-    from fft_wgpu_amd import strided as s
-    s.lib()
-    return s
+    return side_libs.load("strided")
 
 
 def _header_functions():
